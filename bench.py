@@ -5,7 +5,10 @@ One "step" = one random-access B-frame's worth of havoc primitive calls (turingc
 counts the reference encoder issues per 1920x1080 B-frame at QP32 speed=medium), evaluated
 by the batch kernels of libhavoc_mi355x.so with every operand already resident in HBM.  value = frames per second.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--res 1920x1080] [--bit-depth 8]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--res 1920x1080] [--bit-depth 8] [--dump-outputs DIR]
+
+The timed region is exactly K steps after W warm-up steps (`ms_per_step` = its time / K; --min-seconds repeats it); --dump-outputs writes what
+the last of them computed.
 
 N > 1 is launched by the driver through torch.distributed.run (one rank per GPU, RCCL): frames are sharded across
 ranks (each rank works on its own picture: weak scaling) and after every step the ranks holding reference pictures
@@ -55,8 +58,12 @@ def parse_args():
     ap.add_argument("--mix", choices=["ra", "ai"], default="ra",
                     help="call mix: one random-access B-frame at speed=medium (default) or one all-intra frame at speed=fast "
                          "(BASELINE.json configs[0]: intra + TU chain with havoc_quantize in it)")
-    ap.add_argument("--min-seconds", type=float, default=0.5,
-                    help="the K-step timed block is repeated until this much time has been measured; the median block is reported")
+    ap.add_argument("--min-seconds", type=float, default=None,
+                    help="repeat the K-step timed block until this much time has been measured and report the median block (default: ONE block, "
+                         "so that --steps is the number of timed steps); 0 = one block and no counter passes (runs under a profiler)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write every result buffer of the last timed step's picture as DIR/<name>.npy (float32 for 8- / 16-bit "
+                         "results, float64 for 32-bit ones; buffers above a per-buffer share of 64 MB as a fixed seeded sample of their elements)")
     ap.add_argument("--extra-4k", type=int, default=1,
                     help="also measure the 3840x2160 8-bit QP27 workload (BASELINE.json configs[2]) for a few steps and report it under "
                          "`extra` (N=1 only; 0 = off)")
@@ -804,6 +811,29 @@ def timed_blocks(torch, dist, world, steps, min_seconds, run_block, max_blocks=6
         total += dt
         if total >= min_seconds or len(out) >= max_blocks:
             return out
+
+
+DUMP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(torch, dev, out_dir):
+    """--dump-outputs: every result buffer of `dev` (DeviceFrame.outputs) as out_dir/<name>.npy, 8- / 16-bit values as float32 and 32-bit ones as
+    float64 (both exact).  A buffer above its share of DUMP_BYTES is written as the elements at a fixed sample of indices, seeded by its name and
+    length, so that two builds run with the same arguments write the same elements.  Returns {name: [elements written, elements in the buffer]}."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    bufs = dev.outputs()
+    cap = (DUMP_BYTES - 256 * len(bufs)) // (8 * len(bufs))      # (256: room for each file's .npy header)
+    written = {}
+    for name, (t, dtype) in bufs.items():
+        n = t.numel()
+        if n > cap:
+            rng = np.random.default_rng([zlib.crc32(name.encode()), n])
+            t = t[torch.from_numpy(np.unique(rng.integers(0, n, cap))).to(t.device)]
+        a = t.cpu().numpy().view(dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32 if a.itemsize <= 2 else np.float64))
+        written[name] = [int(a.size), int(n)]
+    return written
 
 
 def decision_frame_parallel(args, torch, dist, Havoc, rank, world, local):
@@ -1777,7 +1807,7 @@ def main():
                 one_step(base[0] + i)
             base[0] += args.steps
         before = pipe.pictures if pipe is not None else 0
-        blocks = timed_blocks(torch, dist, world, args.steps, args.min_seconds, run_block)
+        blocks = timed_blocks(torch, dist, world, args.steps, args.min_seconds or 0.0, run_block)
         # frame-parallel steady state: every rank works on one picture per slot (DagSchedule); counted, not assumed
         if pipe is not None:
             n = torch.tensor([pipe.pictures - before], device="cuda", dtype=torch.float64)
@@ -1786,6 +1816,11 @@ def main():
             pictures_per_block = float(n.item()) / len(blocks)
         else:
             pictures_per_block = float(world * args.steps)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the last timed step computed (its picture context), before the kernel times, counter passes and extras below launch again
+        last = (pipe.count - 1) % len(slots) if pipe is not None else (base[0] - 1) % inflight
+        dumped = dump_outputs(torch, slots[last][3], args.dump_outputs)
     blk = float(np.median(blocks))
     elapsed = blk
     all_poc = None
@@ -1814,7 +1849,7 @@ def main():
         ach = unique[dom] / (ktimes[dom] * 1e-3) / 1e9
         total_bytes = sum(kbytes[k] for k in ktimes)
         traffic, traffic_source, valu = None, None, None
-        if world == 1 and not (args.pcie or args.skip or args.no_graph) and args.min_seconds > 0:
+        if world == 1 and not (args.pcie or args.skip or args.no_graph) and args.min_seconds != 0:
             c = counters_in_run(args, dom, wl.S, also=("rdoq",) if dom != "rdoq" and "rdoq" in ktimes else ())
             if "FETCH_SIZE" in c and "WRITE_SIZE" in c:
                 traffic = round(c["FETCH_SIZE"] + c["WRITE_SIZE"])
@@ -1835,7 +1870,7 @@ def main():
         # the launch group furthest below any roofline is in the line too: `rdoq` -- several kernels of dependent decision chains per step
         worst = None
         if "rdoq" in ktimes and dom != "rdoq":
-            wc = (c.get("also", {}).get("rdoq", {}) if world == 1 and not (args.pcie or args.skip or args.no_graph) and args.min_seconds > 0 else {})      # (`c`: the counter passes above)
+            wc = (c.get("also", {}).get("rdoq", {}) if world == 1 and not (args.pcie or args.skip or args.no_graph) and args.min_seconds != 0 else {})      # (`c`: the counter passes above)
             wa = kbytes["rdoq"] / (ktimes["rdoq"] * 1e-3) / 1e9
             worst = {"bound": "hbm", "kernel": "rdoq", "achieved": round(wa, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(wa / HBM_PEAK_GBS, 5),
                      "traffic": round(wc["FETCH_SIZE"] + wc["WRITE_SIZE"]) if "FETCH_SIZE" in wc and "WRITE_SIZE" in wc else None,
@@ -1885,6 +1920,8 @@ def main():
                            "kernel_gbs": {k: round(kbytes[k] / (v * 1e-3) / 1e9, 1) for k, v in ktimes.items()}},
             "checksum": dev.checksum(),
         }
+        if dumped is not None:
+            out["outputs_dumped"] = {"dir": args.dump_outputs, "elements_written_of_buffer": dumped}
         if pipe is not None:
             out["config"]["parallelism"] = (
                 f"frame-parallel x{world}: hierarchical-B docket (turing/InputQueue.cpp:370-379) list-scheduled on {world} ranks "

@@ -347,19 +347,33 @@ class DeviceFrame:
             cnt[name] = cnt.get(name, 0) + 1
         return t, cnt
 
+    def outputs(self):
+        """every result buffer of the step: {name: (device tensor, numpy dtype of its values)} -- the tensors hold uint16 / uint32 values as
+        int16 / int32 bits (Havoc.zeros)"""
+        dt, i16, i32, u32 = self.wl.dtype, np.int16, np.int32, np.uint32
+        ime_name, ime = ("sad4", self.o_sad4) if self.ime_range is None else ("sad_surface", self.o_surf)
+        out = {ime_name: (ime, i32), "sad": (self.o_sad, i32), "satd_inter": (self.o_satd, i32), "pred": (self.pred, dt), "cpred": (self.cpred, dt), "bi": (self.bi, dt),
+               "cbi": (self.cbi, dt), "sbi": (self.sbi, dt)}
+        for log2, g in self.intra.items():
+            out[f"intra{log2}"] = (g["dst"], dt)
+        for log2, g in self.isearch.items():
+            out[f"intra_satd35_{log2}"] = (g["cost"], i32)
+        for c, g in (self.subpel_planes if self.use_planes else self.subpel).items():
+            out["subpel_" + ("x".join(map(str, c)) if isinstance(c, tuple) else str(c))] = (g["cost"], i32)
+        for (log2, tr), g in self.tu.items():
+            for k, d in (("res", i16), ("coef", i16), ("level", i16), ("deq", i16), ("rec", dt), ("ossd", u32), ("ossd_x", u32)):
+                out[f"tu{log2}_{tr}_{k}"] = (g[k], d)
+        out["recon_luma"] = (self.luma[3 * self.wl.plane_len:], dt)
+        out["recon_chroma"] = (self.chroma[3 * self.wl.cplane_len:], dt)
+        for (comp, log2), g in self.recon.items():
+            out[f"recon_{comp}{log2}_ssd"] = (g["ssd"], u32)
+        return out
+
     def checksum(self):
         """a checksum of checksums over every result buffer (size-independent parity property; see tests)"""
         import torch
         acc = 0
-        bufs = [self.o_sad4 if self.ime_range is None else self.o_surf, self.o_sad, self.o_satd, self.pred, self.cpred, self.bi, self.cbi, self.sbi]
-        for g in self.intra.values():
-            bufs += [g["dst"]]
-        for g in list(self.isearch.values()) + list(self.subpel_planes.values() if self.use_planes else self.subpel.values()):
-            bufs += [g["cost"]]
-        for g in self.tu.values():
-            bufs += [g["res"], g["coef"], g["level"], g["deq"], g["rec"], g["ossd"], g["ossd_x"]]
-        bufs += [self.luma[3 * self.wl.plane_len:], self.chroma[3 * self.wl.cplane_len:]] + [g["ssd"] for g in self.recon.values()]
-        for b in bufs:
+        for b, _ in self.outputs().values():
             acc = (acc * 1000003 + int(b.to(torch.int64).sum().item())) & 0xFFFFFFFFFFFF
         return acc
 
