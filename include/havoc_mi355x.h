@@ -489,6 +489,62 @@ typedef struct {
 int havoc_mi355x_sao_filter(havoc_mi355x_ctx *ctx, int S, int bitDepth, void *d_dst, intptr_t stride_dst, const void *d_src, intptr_t stride_src,
                             const havoc_mi355x_sao_job *d_jobs, int njobs);
 
+/* The SAO parameters of a picture's CTUs and their distortion: EncSao::saoRdEstimateLuma / saoRdEstimateChroma (turing/EncSao.h:286-797)
+ * and EncSao::computeSaoDistortion (EncSao.h:800-947), in one call on the context's stream (no host synchronisation, no allocation:
+ * capturable into a graph).  Per CTU:
+ *   1. statistics -- havoc_mi355x_sao_stats on Y, on Cb and on Cr (summed per class and category, EncSao.h:586-587), the joint
+ *      chroma band histogram of havoc_mi355x_sao_band_chroma;
+ *   2. estimation -- luma and chroma each decided over off, edge classes 0..3 and band positions startBand..0 exactly as the
+ *      reference's sequential loop: double arithmetic without fused multiply-add, strict `<` (the first candidate wins a tie), the
+ *      search starting from a cost of 0.0 (a type is chosen only below 0), a type whose four offsets are all 0 is off.  The reference's
+ *      quirks are kept: roundSao by bit depth (EncSao.h:42-48), the vertical class rounding an INTEGER quotient (EncSao.h:369),
+ *      estSaoDist shifting the magnitude (EncSao.h:49-59), the offset limit (1 << (min(bitDepth, 10) - 5)) - 1, band offsets
+ *      estimated from bands bandPosition .. bandPosition + 3 where startBand is one past the densest four-band window (EncSao.h:106,
+ *      :485).  One difference: at band position 29 the reference reads one element past its int64[32] band arrays (EncSao.h:485,
+ *      :749, band 32); here band 32 is empty.  bitDepth is both BitDepthY and BitDepthC (the chroma edge clamp's else-branch reads
+ *      BitDepthY, EncSao.h:590; the chroma filters get BitDepthY, EncSao.h:921-929).
+ *   3. apply and measure -- the CTU's Y, Cb, Cr filtered with the estimated parameters into d_dst_* (LoopFilter.h:134-160
+ *      SaoOffsetVal; the band table of EncSao.h:866-877, whose four entries wrap at band 31; a component that is off is copied),
+ *      and EncSao::ssd against the source: uint32 accumulation that wraps, >> 4 for 16-bit samples whatever the bit depth.
+ * lambda: reciprocal_lambda_q16 is the encoder's reciprocal lambda, FixedPoint<int32_t, 16> (turing/Cost.h:34, Measure.h:44), > 0;
+ * the search uses 1 / (reciprocal_lambda_q16 / 65536.0).  flags: bit 0 = slice_sao_luma_flag, bit 1 = slice_sao_chroma_flag; a
+ * disabled component is type 0.  Pictures are 4:2:0: a luma plane and one chroma plane holding Cb and Cr (offsets in samples, one
+ * stride per plane and picture).  The edge filter reads one sample beyond the CTU on every side, from the reconstruction: every
+ * plane needs that margin around the picture.  d_dst_* must differ from d_rec_*.  A CTU record whose w or h is odd or outside
+ * 8..64 gets an all-zero parameter record and nothing of it is written.
+ * d_work: havoc_mi355x_sao_workspace(nctus) bytes of device scratch, 16-byte aligned, private to the call until it completes. */
+typedef struct {
+    int32_t src_y, src_cb, src_cr;   /* the CTU's Y / Cb / Cr block in the source planes */
+    int32_t rec_y, rec_cb, rec_cr;   /* ... in the (deblocked) reconstruction */
+    int32_t dst_y, dst_cb, dst_cr;   /* ... in the destination */
+    int32_t w, h;                    /* luma size clipped to the picture, even, 8..64; chroma is (w / 2) x (h / 2) */
+    int32_t reserved;
+    /* where the chroma statistics are read (source, reconstruction): the CTU's own blocks (= src_cb .. rec_cr), or, to reproduce the
+     * reference bit for bit, where saoRdEstimateChroma reads them: EncSao.h:534-546 passes chroma coordinates to ThreePlanes::operator()
+     * (Picture.h:179-187), which halves them again -- the block at (x / 4, y / 4) of the chroma planes. */
+    int32_t stat_src_cb, stat_src_cr, stat_rec_cb, stat_rec_cr;
+} havoc_mi355x_sao_ctu; /* 64 bytes */
+typedef struct {
+    int32_t type;                    /* SaoTypeIdx: 0 off, 1 band offset, 2 edge offset */
+    int32_t eo_class;                /* SaoEoClass when type 2, else 0 */
+    int32_t band_position;           /* sao_band_position when type 1, else 0 */
+    int32_t offset_abs[4];           /* sao_offset_abs (EncSao.h:519-524) */
+    int32_t offset_sign[4];          /* sao_offset_sign when type 1, else 0 */
+} havoc_mi355x_sao_component; /* 44 bytes */
+typedef struct {
+    havoc_mi355x_sao_component comp[2];   /* [0] luma, [1] chroma (Cb and Cr share type, class, band and offsets) */
+    int32_t dist_sao;                /* computeSaoDistortion with these parameters: ssd_sao[0] + 4 ssd_sao[1] + 4 ssd_sao[2] (mod 2^32) */
+    int32_t dist_off;                /* ... with both types 0 */
+    uint32_t ssd_sao[3], ssd_off[3]; /* EncSao::ssd per plane Y, Cb, Cr (unscaled): source vs destination / vs reconstruction */
+    int32_t reserved[2];
+} havoc_mi355x_sao_params; /* 128 bytes */
+size_t havoc_mi355x_sao_workspace(int nctus);
+int havoc_mi355x_sao_estimate(havoc_mi355x_ctx *ctx, int S, int bitDepth, int32_t reciprocal_lambda_q16, int flags,
+                              const void *d_src_y, const void *d_src_c, intptr_t stride_src_y, intptr_t stride_src_c,
+                              const void *d_rec_y, const void *d_rec_c, intptr_t stride_rec_y, intptr_t stride_rec_c,
+                              void *d_dst_y, void *d_dst_c, intptr_t stride_dst_y, intptr_t stride_dst_c,
+                              const havoc_mi355x_sao_ctu *d_ctus, int nctus, void *d_work, size_t work_bytes, havoc_mi355x_sao_params *d_params);
+
 /* ------------------------------------------------------------------------------------------------------- */
 /* rate-distortion optimised quantisation                                                 */
 /* ------------------------------------------------------------------------------------------------------- */

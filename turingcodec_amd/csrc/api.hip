@@ -63,6 +63,9 @@ size_t rdoq_workspace_bytes(int njobs);
 hipError_t launch_sao_stats(hipStream_t, int S, int bd, const void *, long, const void *, long, const void *, int, int64_t *);
 hipError_t launch_sao_band_chroma(hipStream_t, int S, int bd, const void *, long, const void *, long, const void *, int, int64_t *);
 hipError_t launch_sao_filter(hipStream_t, int S, int bd, void *, long, const void *, long, const void *, int);
+size_t sao_workspace_bytes(int nctus);
+hipError_t launch_sao_estimate(hipStream_t, int S, int bd, double lambda, int flags, const void *, const void *, long, long, const void *, const void *, long, long,
+                               void *, void *, long, long, const void *, int, void *, void *);
 hipError_t launch_quantize_inverse(hipStream_t, int16_t *, const int16_t *, const void *, int);
 hipError_t launch_quantize_reconstruct(hipStream_t, int log2, uint8_t *, long, const uint8_t *, long, const int16_t *, const void *, int);
 hipError_t launch_residual(hipStream_t, int S, int16_t *, long, const int32_t *, const void *, long, const void *, long, const void *, int);
@@ -82,6 +85,9 @@ static_assert(sizeof(havoc_mi355x_tu_job) == 16, "job ABI");
 static_assert(sizeof(havoc_mi355x_intra_search_job) == 32, "job ABI");
 static_assert(sizeof(havoc_mi355x_tu_fused_job) == 16, "job ABI");
 static_assert(sizeof(havoc_mi355x_quant_job) == 32, "job ABI");
+static_assert(sizeof(havoc_mi355x_sao_ctu) == 64 && sizeof(havoc_mi355x_sao_component) == 44 && sizeof(havoc_mi355x_sao_params) == 128, "sao record ABI");
+static_assert(offsetof(havoc_mi355x_sao_params, dist_sao) == 88 && offsetof(havoc_mi355x_sao_params, ssd_sao) == 96 && offsetof(havoc_mi355x_sao_ctu, stat_src_cb) == 48,
+              "sao record ABI");
 static_assert(sizeof(havoc_mi355x_intra_mpm) == 40 && sizeof(havoc_mi355x_intra_choice) == 40, "job ABI");
 
 #include "ctx.h"
@@ -909,6 +915,27 @@ int havoc_mi355x_sao_filter(havoc_mi355x_ctx *ctx, int S, int bitDepth, void *d_
     REQUIRE_CTX(); REQUIRE(S == 1 || S == 2, "S must be 1 or 2"); REQUIRE_BD(); REQUIRE(njobs >= 0, "njobs < 0");
     REQUIRE(d_dst != d_src, "sao_filter: the filtered picture and the deblocked picture must be different buffers");
     return check(launch_sao_filter(LS(ctx), S, bitDepth, d_dst, stride_dst, d_src, stride_src, d_jobs, njobs), "sao_filter");
+}
+
+size_t havoc_mi355x_sao_workspace(int nctus) { return sao_workspace_bytes(nctus); }
+
+int havoc_mi355x_sao_estimate(havoc_mi355x_ctx *ctx, int S, int bitDepth, int32_t reciprocal_lambda_q16, int flags, const void *d_src_y, const void *d_src_c,
+                              intptr_t stride_src_y, intptr_t stride_src_c, const void *d_rec_y, const void *d_rec_c, intptr_t stride_rec_y, intptr_t stride_rec_c,
+                              void *d_dst_y, void *d_dst_c, intptr_t stride_dst_y, intptr_t stride_dst_c, const havoc_mi355x_sao_ctu *d_ctus, int nctus,
+                              void *d_work, size_t work_bytes, havoc_mi355x_sao_params *d_params)
+{
+    REQUIRE_CTX(); REQUIRE_S(); REQUIRE_BD(); REQUIRE(nctus >= 0, "nctus < 0");
+    REQUIRE(reciprocal_lambda_q16 > 0, "sao_estimate: reciprocal_lambda_q16 must be > 0");
+    REQUIRE(flags >= 0 && flags <= 3, "sao_estimate: flags = bit 0 luma, bit 1 chroma");
+    REQUIRE(nctus == 0 || (d_src_y && d_src_c && d_rec_y && d_rec_c && d_dst_y && d_dst_c && d_ctus && d_params), "sao_estimate: null plane, CTU or parameter pointer");
+    REQUIRE(d_dst_y != d_rec_y && d_dst_c != d_rec_c, "sao_estimate: the filtered picture and the reconstruction must be different buffers");
+    REQUIRE(nctus == 0 || (d_work && work_bytes >= sao_workspace_bytes(nctus) && (reinterpret_cast<uintptr_t>(d_work) & 15) == 0),
+            "sao_estimate: workspace missing, misaligned or smaller than havoc_mi355x_sao_workspace(nctus)");
+    // the lambda the reference searches with, 1 / Lambda::asDouble() (turing/EncSao.h:322-323, FixedPoint.h:60): rounded on the host
+    const double lambda = 1 / ((double)reciprocal_lambda_q16 / (double)(1 << 16));
+    return check(launch_sao_estimate(LS(ctx), S, bitDepth, lambda, flags, d_src_y, d_src_c, stride_src_y, stride_src_c, d_rec_y, d_rec_c, stride_rec_y,
+                                     stride_rec_c, d_dst_y, d_dst_c, stride_dst_y, stride_dst_c, d_ctus, nctus, d_work, d_params),
+                 "sao_estimate");
 }
 
 int havoc_mi355x_tu_forward_scan(havoc_mi355x_ctx *ctx, int S, int bitDepth, int log2TrafoSize, int16_t *d_coeffs, const void *d_src, intptr_t stride_src,

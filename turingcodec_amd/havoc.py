@@ -130,11 +130,14 @@ def _load():
         "sao_stats": [_vp, _i, _i, _vp, _ip, _vp, _ip, _vp, _i, _vp],
         "sao_filter": [_vp, _i, _i, _vp, _ip, _vp, _ip, _vp, _i],
         "sao_band_chroma": [_vp, _i, _i, _vp, _ip, _vp, _ip, _vp, _i, _vp],
+        "sao_estimate": [_vp, _i, _i, C.c_int32, _i, _vp, _vp, _ip, _ip, _vp, _vp, _ip, _ip, _vp, _vp, _ip, _ip, _vp, _i, _vp, C.c_size_t, _vp],
     }
     L.havoc_mi355x_rdoq_lambda.argtypes = [C.c_double, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.havoc_mi355x_rdoq_lambda.restype = None
     L.havoc_mi355x_rdoq_workspace.argtypes = [_i]
     L.havoc_mi355x_rdoq_workspace.restype = C.c_size_t
+    L.havoc_mi355x_sao_workspace.argtypes = [_i]
+    L.havoc_mi355x_sao_workspace.restype = C.c_size_t
     L.havoc_mi355x_search_workspace.argtypes = [_i, _i]
     L.havoc_mi355x_search_workspace.restype = C.c_size_t
     for name, args in sig.items():
@@ -148,7 +151,7 @@ def exported_symbols():
     """names the C ABI must export (checked against include/havoc_mi355x.h by the CPU tests)"""
     _, names = _load()
     return ["havoc_mi355x_" + n for n in names] + ["havoc_mi355x_last_error", "havoc_mi355x_version", "havoc_mi355x_rdoq_lambda", "havoc_mi355x_rdoq_workspace",
-                                                "havoc_mi355x_search_workspace"]
+                                                "havoc_mi355x_search_workspace", "havoc_mi355x_sao_workspace"]
 
 
 # one havoc_mi355x_cell (include/havoc_mi355x.h), 16 bytes: a 4x4 luma cell of a picture's block structure
@@ -160,6 +163,49 @@ CELL_INTRA, CELL_CODED, CELL_NO_FILTER, CELL_PU_LEFT, CELL_PU_TOP = 1, 2, 4, 8, 
 SAO_JOB_DT = np.dtype([("dst_off", "<i4"), ("src_off", "<i4"), ("w", "<i4"), ("h", "<i4"), ("type", "<i4"), ("eo_class", "<i4"), ("offsets", "<i2", 32),
                        ("reserved", "<i4", 2)])
 assert SAO_JOB_DT.itemsize == 96
+
+# one havoc_mi355x_sao_ctu (include/havoc_mi355x.h), 64 bytes: a CTU's blocks in the source, reconstruction and destination planes
+SAO_CTU_DT = np.dtype([("src_y", "<i4"), ("src_cb", "<i4"), ("src_cr", "<i4"), ("rec_y", "<i4"), ("rec_cb", "<i4"), ("rec_cr", "<i4"),
+                       ("dst_y", "<i4"), ("dst_cb", "<i4"), ("dst_cr", "<i4"), ("w", "<i4"), ("h", "<i4"), ("reserved", "<i4"),
+                       ("stat_src_cb", "<i4"), ("stat_src_cr", "<i4"), ("stat_rec_cb", "<i4"), ("stat_rec_cr", "<i4")])
+assert SAO_CTU_DT.itemsize == 64
+
+# one havoc_mi355x_sao_params (include/havoc_mi355x.h), 128 bytes: comp[0] luma, comp[1] chroma (Cb and Cr share it)
+SAO_COMPONENT_DT = np.dtype([("type", "<i4"), ("eo_class", "<i4"), ("band_position", "<i4"), ("offset_abs", "<i4", 4), ("offset_sign", "<i4", 4)])
+SAO_PARAMS_DT = np.dtype([("comp", SAO_COMPONENT_DT, 2), ("dist_sao", "<i4"), ("dist_off", "<i4"), ("ssd_sao", "<u4", 3), ("ssd_off", "<u4", 3),
+                          ("reserved", "<i4", 2)])
+assert SAO_COMPONENT_DT.itemsize == 44 and SAO_PARAMS_DT.itemsize == 128
+
+
+def sao_layout(width, height, pad=8):
+    """A padded 4:2:0 picture layout for havoc_mi355x_sao_estimate: a luma plane of (height + 2 pad) rows of stride width + 2 pad, and one
+    chroma plane holding Cb then Cr, each (height / 2 + pad) rows of stride width / 2 + pad.  The edge filter reads one sample beyond every
+    CTU, so pad >= 2.  -> dict: pad, stride_y, stride_c, size_y (samples of the luma plane), size_c (samples of ONE chroma component)."""
+    assert pad >= 2 and pad % 2 == 0 and width % 2 == 0 and height % 2 == 0
+    sy, sc = width + 2 * pad, width // 2 + pad
+    return dict(pad=pad, stride_y=sy, stride_c=sc, size_y=sy * (height + 2 * pad), size_c=sc * (height // 2 + pad))
+
+
+def sao_ctu_table(width, height, ctb_size, pad=8, chroma_stats="ctu"):
+    """SAO_CTU_DT records of every CTU of a width x height picture in raster order, for source, reconstruction and destination all in
+    sao_layout(width, height, pad); the CTUs of the last column / row are clipped to the picture (EncSao.h:290-297).
+    chroma_stats: where the chroma decision reads its statistics -- "ctu": the CTU's own Cb / Cr blocks; "reference": where
+    saoRdEstimateChroma reads them (EncSao.h:534-546 halves the chroma position a second time through ThreePlanes::operator(),
+    Picture.h:179-187: the block at (x / 4, y / 4) of the chroma plane, of the CTU's chroma size)."""
+    assert ctb_size in (16, 32, 64) and chroma_stats in ("ctu", "reference")
+    L = sao_layout(width, height, pad)
+    sy, sc, p, pc = L["stride_y"], L["stride_c"], pad, pad // 2
+    rows = []
+    for y in range(0, height, ctb_size):
+        for x in range(0, width, ctb_size):
+            w, h = min(ctb_size, width - x), min(ctb_size, height - y)
+            oy = (y + p) * sy + x + p
+            ocb = (y // 2 + pc) * sc + x // 2 + pc
+            ocr = L["size_c"] + ocb
+            scb = ocb if chroma_stats == "ctu" else (y // 4 + pc) * sc + x // 4 + pc
+            rows.append((oy, ocb, ocr, oy, ocb, ocr, oy, ocb, ocr, w, h, 0, scb, L["size_c"] + scb, scb, L["size_c"] + scb))
+    return np.array(rows, np.int32).view(SAO_CTU_DT).reshape(-1)
+
 
 # one havoc_mi355x_rdoq_job (include/havoc_mi355x.h), 48 bytes
 RDOQ_JOB_DT = np.dtype([("dst_off", "<i4"), ("src_off", "<i4"), ("quant_scale", "<i4"), ("quant_shift", "<i4"), ("inv_scale", "<i4"),
@@ -596,6 +642,34 @@ class Havoc:
             j = self.torch.from_numpy(jobs.view(np.uint8).reshape(-1)).to(self.device)
         self._ck(self.L.havoc_mi355x_sao_filter(self.h, self._S(s), bd, _ptr(dst), sd, _ptr(s), ss, _ptr(j), len(jobs)))
         return self.down(dst, dst_like.dtype)
+
+    def sao_workspace(self, nctus):
+        """device scratch for one sao_estimate call over `nctus` CTUs (an int64 tensor: 16-byte aligned)"""
+        n = int(self.L.havoc_mi355x_sao_workspace(int(nctus)))
+        with self.torch.cuda.stream(self.tstream):
+            return self.torch.zeros((n + 7) // 8 + 2, dtype=self.torch.int64, device=self.device)
+
+    def sao_estimate_d(self, bd, lambda_q16, flags, src_y, src_c, ssy, ssc, rec_y, rec_c, rsy, rsc, dst_y, dst_c, dsy, dsc, ctus, work, params):
+        """device level: ctus = uint8 tensor of SAO_CTU_DT records, params = uint8 tensor of as many SAO_PARAMS_DT records; no
+        synchronisation and no allocation (graph capture)"""
+        self._ck(self.L.havoc_mi355x_sao_estimate(self.h, self._S(src_y), bd, int(lambda_q16), int(flags), _ptr(src_y), _ptr(src_c), ssy, ssc,
+                                                  _ptr(rec_y), _ptr(rec_c), rsy, rsc, _ptr(dst_y), _ptr(dst_c), dsy, dsc,
+                                                  _ptr(ctus), ctus.numel() // SAO_CTU_DT.itemsize, _ptr(work), work.numel() * 8, _ptr(params)))
+
+    def sao_estimate(self, bd, lambda_q16, src_y, src_c, rec_y, rec_c, stride_y, stride_c, ctus, flags=3):
+        """numpy level: the SAO parameters of every CTU of `ctus` (SAO_CTU_DT; one layout for source, reconstruction and destination,
+        e.g. sao_ctu_table) -> (SAO_PARAMS_DT records, filtered luma plane, filtered chroma plane); the destination starts as a copy of
+        the reconstruction, so samples outside every CTU keep it"""
+        ctus = np.ascontiguousarray(ctus, SAO_CTU_DT)
+        torch = self.torch
+        sy, sc, ry, rc = self.up(src_y), self.up(src_c), self.up(rec_y), self.up(rec_c)
+        with torch.cuda.stream(self.tstream):
+            dy, dc = ry.clone(), rc.clone()
+            d_ctus = torch.from_numpy(ctus.view(np.uint8).reshape(-1)).to(self.device)
+            params = torch.zeros(len(ctus) * SAO_PARAMS_DT.itemsize, dtype=torch.uint8, device=self.device)
+        self.sao_estimate_d(bd, lambda_q16, flags, sy, sc, stride_y, stride_c, ry, rc, stride_y, stride_c, dy, dc, stride_y, stride_c, d_ctus,
+                            self.sao_workspace(len(ctus)), params)
+        return self.down(params, np.uint8).view(SAO_PARAMS_DT), self.down(dy, rec_y.dtype), self.down(dc, rec_c.dtype)
 
     def rdoq_workspace(self, njobs):
         """device scratch for one rdoq launch of `njobs` blocks (an int64 tensor: 16-byte aligned)"""
