@@ -5,10 +5,12 @@ One "step" = one random-access B-frame's worth of havoc primitive calls (turingc
 counts the reference encoder issues per 1920x1080 B-frame at QP32 speed=medium), evaluated
 by the batch kernels of libhavoc_mi355x.so with every operand already resident in HBM.  value = frames per second.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--res 1920x1080] [--bit-depth 8] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--res 1920x1080] [--bit-depth 8] [--dump-outputs DIR] [--full]
 
 The timed region is exactly K steps after W warm-up steps (`ms_per_step` = its time / K; --min-seconds repeats it); --dump-outputs writes what
-the last of them computed.
+the last of them computed.  A plain run does only that: set up, warm up, time, dump, print the line.  --full also measures and checks everything
+around the headline: per-kernel times and the roofline (with counter passes of their own), the 4K and 10-bit configurations, the step without
+RDOQ, the one-picture latency, the decision-driven path, the CPU baselines and the parity check against the reference library.
 
 N > 1 is launched by the driver through torch.distributed.run (one rank per GPU, RCCL): frames are sharded across
 ranks (each rank works on its own picture: weak scaling) and after every step the ranks holding reference pictures
@@ -29,7 +31,7 @@ sys.path.insert(0, ROOT)
 
 # HIP maps streams onto 4 hardware queues unless told otherwise: with more independent pictures in flight than queues, their kernels (the
 # one-launch-per-picture search above all) queue up behind each other.  Must be in the environment before the runtime starts, so the
-# decision-driven path is measured in a process of its own (`--decisions 2`, started by the plain run) with 16 queues; the primitive-batch
+# decision-driven path is measured in a process of its own (`--decisions 2`, started by a --full run) with 16 queues; the primitive-batch
 # step keeps the runtime's default (its 8 lanes are branches of one HIP graph; measured slower with 16 queues: 0.62 against 0.49 ms).
 if "--decisions" in sys.argv[:-1] and sys.argv[sys.argv.index("--decisions") + 1] in ("2", "4"):
     # (--vr-bands: three streams per picture context, and what WAITS on a stream must never sit in a hardware queue in front of what it waits for)
@@ -64,13 +66,17 @@ def parse_args():
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write every result buffer of the last timed step's picture as DIR/<name>.npy (float32 for 8- / 16-bit "
                          "results, float64 for 32-bit ones; buffers above a per-buffer share of 64 MB as a fixed seeded sample of their elements)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything around the headline (see the top of this file): the options "
+                         "--extra-4k, --decisions 1, --traffic, --kernel-reps and --no-cpu-baseline shape what it adds; without --full the run "
+                         "prints the headline alone")
     ap.add_argument("--extra-4k", type=int, default=1,
-                    help="also measure the 3840x2160 8-bit QP27 workload (BASELINE.json configs[2]) for a few steps and report it under "
+                    help="with --full: also measure the 3840x2160 8-bit QP27 workload (BASELINE.json configs[2]) for a few steps and report it under "
                          "`extra` (N=1 only; 0 = off)")
     ap.add_argument("--bands", type=int, default=0, help="frame-parallel runs: exchange the reference pictures in bands of this many CTU rows (turingcodec_amd/"
                     "frame_parallel.py: BandPlan; 0 = one broadcast per picture)")
     ap.add_argument("--decisions", type=int, default=1,
-                    help="1 (default): the plain N=1 line also carries, under `extra`, the DECISION-DRIVEN path (turingcodec_amd.decisions."
+                    help="1 (default): with --full, the N=1 line also carries, under `extra`, the DECISION-DRIVEN path (turingcodec_amd.decisions."
                          "DecisionPicture: motion searches in WPP wavefront order with predictors derived from earlier decisions, batch-fed; then the "
                          "TU chain on the chosen vectors) at 1080p QP32 and 4K QP32, and its ratio to `value`; 2: only that (diagnostic line); 0: off")
     ap.add_argument("--vr-bands", type=int, default=0, help="--decisions 4: CTU rows per band -- a picture's reconstruction enters the mirror band by band while its lower rows "
@@ -84,17 +90,17 @@ def parse_args():
     ap.add_argument("--decision-pictures", type=int, default=16, help="contexts built for the decision-driven path: `value` is measured with 4 independent pictures in flight (the "
                     "leaf B pictures of one SOP), and again with 8 (what the pipelined hierarchy has in flight) and with all of them; one host thread + "
                     "context each")
-    ap.add_argument("--traffic", type=int, default=1, help="1 (default): the plain N=1 run measures roofline.traffic itself with two rocprofv3 --pmc passes "
+    ap.add_argument("--traffic", type=int, default=1, help="1 (default): a --full N=1 run measures roofline.traffic itself with two rocprofv3 --pmc passes "
                     "of a two-step run (when rocprofv3 is on PATH); 0: take it from the committed profiles/r*_hbm_traffic.csv")
     ap.add_argument("--traffic-child", type=int, default=0, help=argparse.SUPPRESS)      # the counter passes' child: exactly this many steps, eagerly, then exit
     ap.add_argument("--decision-distance", type=int, default=1, help="with --decisions 2: temporal distance of the decision-driven picture's two references "
                     "(1 = a leaf B picture of the hierarchy; 2, 4, 8 = its upper layers: longer vectors, 2.5 - 3 x the calls per search)")
     ap.add_argument("--decision-walk", type=int, default=0, help="with --decisions 2: also time the same walk through the reference's tables on one host core "
-                    "and compare every decision (the cpu_baseline leg of the plain run)")
+                    "and compare every decision (the cpu_baseline leg of a --full run)")
     ap.add_argument("--search-client", choices=["device", "batch"], default="device",
                     help="the motion searches of the decision-driven path: `device` = the decision loops inside the kernel (csrc/kernels_search.hip, one launch "
                          "per picture); `batch` = SAD-surface / tile-SATD launches + the loops replayed on host threads (search/picture_search.cpp)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines and the parity check against the reference library")
     ap.add_argument("--detail-out", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"),
                     help="the FULL result (every `what` / `note` string, per-distance decision-path detail, per-kernel tables) goes to this file; the ONE JSON "
                          "line on stdout stays below 8 KB (the driver keeps 8 KB of it: VERDICT r4 next #1c)")
@@ -104,7 +110,7 @@ def parse_args():
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the cpu_baseline sample")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-out", default=None, help=argparse.SUPPRESS)
-    ap.add_argument("--kernel-reps", type=int, default=5)
+    ap.add_argument("--kernel-reps", type=int, default=5, help="with --full: launches averaged per launch group for the per-kernel times of the roofline")
     ap.add_argument("--sad4", choices=["runs", "calls"], default="runs",
                     help="the 4-way SAD jobs: by runs (default; havoc_mi355x_sad4_runs: the ~112 consecutive calls of a search share one staged window, round 5) "
                          "or one window per call (havoc_mi355x_sad4, round 4's k_sad4w)")
@@ -641,6 +647,76 @@ def _kernel_prefix(group, S):
               "subpel_satd": "k_subpel_satd<", "rdoq": "k_rdoq_", "deblock": "k_deblock<"}.get(group)
 
 
+def kernel_figures(args, dev, wl, world, ms_step):
+    """--full: the per-kernel times of the step (HIP events, each launch group alone), the roofline of its dominant and of its worst launch group
+    (with counter passes of a child run: counters_in_run) and a checksum of every result buffer -- the keys `roofline`, `roofline_worst_group`,
+    `whole_step` and `checksum` of the line"""
+    ktimes, kcount = dev.kernel_times_ms(args.kernel_reps)
+    kbytes = wl.algorithmic_bytes()
+    kbytes["sad_surface"] = kbytes["sad_surface"](args.ime_range)
+    # the dominant KERNEL: the launch group whose single launch takes longest (a group's time / its launches per step).  Round 4 picked the group with the largest TOTAL,
+    # which since the run form of sad4 would be `rdoq` -- four to five launches of different kernels per step, none of them the step's longest
+    dom = max(ktimes, key=lambda k: ktimes[k] / kcount[k])
+    # roofline of the dominant launch group (VERDICT r4 next #2).  HBM: `achieved` counts UNIQUE algorithmic bytes -- SURVEY 8(d)'s operands once +
+    # results once per call, except where the calls of one search overlap (sad4: the box of a search's candidates + its source block once per run + 16 B per
+    # call; the per-call figure, which counts every reference sample ~112 times, is kept beside it as `operand_bytes_per_step`), so frac <= 1 by construction
+    # and comparable with `traffic`.  VALU: wavefront-level vector instructions (SQ_INSTS_VALU of a --pmc pass of this run) / duration against the issue peak.
+    unique = dict(kbytes)
+    if dom == "sad4":
+        unique["sad4"] = wl.sad4_unique_bytes()
+    ach = unique[dom] / (ktimes[dom] * 1e-3) / 1e9
+    total_bytes = sum(kbytes[k] for k in ktimes)
+    traffic, traffic_source, valu = None, None, None
+    if world == 1 and not (args.pcie or args.skip or args.no_graph) and args.min_seconds != 0:
+        c = counters_in_run(args, dom, wl.S, also=("rdoq",) if dom != "rdoq" and "rdoq" in ktimes else ())
+        if "FETCH_SIZE" in c and "WRITE_SIZE" in c:
+            traffic = round(c["FETCH_SIZE"] + c["WRITE_SIZE"])
+            traffic_source = ("measured in this run, bytes PER STEP (the unit of algorithmic_bytes_per_step): rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE, one "
+                              "counter per pass, no trace domain) over a child run of exactly two steps of the same workload; FETCH_SIZE x2 per the gfx950 note; "
+                              "summed over every launch of the group's kernels, divided by the steps")
+        if "SQ_INSTS_VALU" in c:
+            insts = c["SQ_INSTS_VALU"]
+            rate = insts / (ktimes[dom] * 1e-3) / 1e9
+            valu = {"insts_per_step": round(insts), "achieved": round(rate, 2), "peak": VALU_PEAK_GINST, "unit": "G wavefront-instructions/s",
+                    "frac": round(rate / VALU_PEAK_GINST, 5)}
+    if traffic is None:
+        traffic = hbm_traffic_from_profiles(dom, wl.S)
+        if traffic is not None:
+            traffic *= kcount[dom]      # the committed summary is per launch: times the group's launches per step (kernels of unequal size: approximate)
+        traffic_source = ("profiles/r*_hbm_traffic.csv (mean per launch x launches per step: approximate): separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this bench (profiles/collect.sh), "
+                          "FETCH_SIZE x2 per the gfx950 note; not re-measured in this run (rocprofv3 not on PATH, --traffic 0, or a diagnostic run)")
+    # the launch group furthest below any roofline is in the line too (VERDICT r5 next #7): `rdoq` -- several kernels of dependent decision chains per step
+    worst = None
+    if "rdoq" in ktimes and dom != "rdoq":
+        wc = (c.get("also", {}).get("rdoq", {}) if world == 1 and not (args.pcie or args.skip or args.no_graph) and args.min_seconds != 0 else {})      # (`c`: the counter passes above)
+        wa = kbytes["rdoq"] / (ktimes["rdoq"] * 1e-3) / 1e9
+        worst = {"bound": "hbm", "kernel": "rdoq", "achieved": round(wa, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(wa / HBM_PEAK_GBS, 5),
+                 "traffic": round(wc["FETCH_SIZE"] + wc["WRITE_SIZE"]) if "FETCH_SIZE" in wc and "WRITE_SIZE" in wc else None,
+                 "group_ms": round(ktimes["rdoq"], 5), "launches_per_step": kcount["rdoq"], "algorithmic_bytes_per_step": kbytes["rdoq"]}
+        if "SQ_INSTS_VALU" in wc:
+            wr = wc["SQ_INSTS_VALU"] / (ktimes["rdoq"] * 1e-3) / 1e9
+            worst["valu"] = {"insts_per_step": round(wc["SQ_INSTS_VALU"]), "achieved": round(wr, 2), "peak": VALU_PEAK_GINST, "frac": round(wr / VALU_PEAK_GINST, 5)}
+    return {
+        "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(ach, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": round(ach / HBM_PEAK_GBS, 5), "traffic": traffic,
+                     "traffic_source": traffic_source,
+                     "launch_ms": round(ktimes[dom] / kcount[dom], 5), "launches_per_step": kcount[dom],
+                     "algorithmic_bytes_per_step": unique[dom], "operand_bytes_per_step": kbytes[dom],
+                     "valu": valu, "valu_busy_pct": valu_busy_from_profiles(dom, wl.S),
+                     "note": ("achieved = unique algorithmic bytes / the group's isolated HIP-event time.  The group is not HBM-bound: its operands are cache- and LDS-resident "
+                              "and what bounds it is instruction issue along short dependent chains -- `valu` is the instruction roofline (SQ_INSTS_VALU / time against "
+                              "256 CUs x 4 SIMDs x 2.4 GHz / 2 cycles per wave64 instruction); `traffic` / `algorithmic_bytes_per_step` says how close the kernel is to "
+                              "touching every byte once")},
+        "roofline_worst_group": worst,
+        # operand_gbs: the per-CALL operand bytes of SURVEY 8(d) over the step time -- NOT an HBM figure (the calls of a search name the same reference samples ~112 times and
+        # the operands are cache- and LDS-resident: it can exceed the HBM peak); the HBM statement is `roofline` (unique bytes, measured traffic)
+        "whole_step": {"operand_bytes": total_bytes, "operand_gbs": round(total_bytes / (ms_step * 1e-3) / 1e9, 2),
+                       "kernel_ms": {k: round(v, 4) for k, v in sorted(ktimes.items(), key=lambda kv: -kv[1])},
+                       "kernel_gbs": {k: round(kbytes[k] / (v * 1e-3) / 1e9, 1) for k, v in ktimes.items()}},
+        "checksum": dev.checksum(),
+    }
+
+
 def parity_problems(out):
     """every comparison with the reference this run made that did NOT come out equal (or could not be made): [] = green"""
     bad = []
@@ -693,17 +769,19 @@ def compact_line(out, args):
                       "parallelism": cfg.get("parallelism_short") or cfg.get("parallelism", "")[:100]}
     t = out.get("timing", {})
     line["timing"] = {k: t[k] for k in ("timed_blocks", "block_seconds_median", "block_seconds_min", "block_seconds_max") if k in t}
-    rf = dict(out.get("roofline", {}))
-    for k in ("note", "traffic_source"):
-        rf.pop(k, None)
-    line["roofline"] = rf
+    if "roofline" in out:
+        rf = dict(out["roofline"])
+        for k in ("note", "traffic_source"):
+            rf.pop(k, None)
+        line["roofline"] = rf
     if out.get("roofline_worst_group"):
         line["roofline_worst_group"] = out["roofline_worst_group"]
     ws = out.get("whole_step", {})
     if ws:
         line["whole_step"] = {"operand_bytes": ws.get("operand_bytes"), "operand_gbs": ws.get("operand_gbs"),
                               "kernel_ms": {k: round(v, 3) for k, v in list(ws.get("kernel_ms", {}).items())[:8]}}
-    line["checksum"] = out.get("checksum")
+    if "checksum" in out:
+        line["checksum"] = out["checksum"]
     cb = out.get("cpu_baseline")
     if isinstance(cb, dict):
         c = {k: cb[k] for k in ("value", "unit", "cores", "kind") if k in cb}
@@ -1651,7 +1729,7 @@ def main():
     if args.cpu_worker:
         return cpu_worker(args)
     early = {}
-    if (args.decisions == 1 and args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.mix == "ra"
+    if (args.full and args.decisions == 1 and args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.mix == "ra"
             and not (args.pcie or args.skip or args.no_graph)):
         early = decision_children(args)
     import torch
@@ -1679,7 +1757,7 @@ def main():
         sys.exit(2)
     if args.decisions == 4:      # one sequence with its picture dependencies, K virtual ranks on this GPU
         return decision_virtual_ranks(args, torch, Havoc)
-    if args.decisions == 2:      # only the decision-driven path of --res / --qp, one line (also how the plain run measures it: see the top of this file)
+    if args.decisions == 2:      # only the decision-driven path of --res / --qp, one line (also how a --full run measures it: see the top of this file)
         keep = {} if args.decision_walk else None
         r = decision_path(args, Havoc, args.res, args.bit_depth, args.qp, max(1, args.decision_pictures), seconds=(1.0 if args.decision_pictures <= 8 else 1.5), keep=keep)
         line = {"metric": "DIAGNOSTIC (decision-driven path only) -- not the benchmark metric", "value": r["value"], "unit": r["unit"],
@@ -1833,52 +1911,8 @@ def main():
                 all_poc.update(d)
 
     if rank == 0:
-        ktimes, kcount = dev.kernel_times_ms(args.kernel_reps)
-        kbytes = wl.algorithmic_bytes()
-        kbytes["sad_surface"] = kbytes["sad_surface"](args.ime_range)
-        # the dominant KERNEL: the launch group whose single launch takes longest (a group's time / its launches per step).  Round 4 picked the group with the largest TOTAL,
-        # which since the run form of sad4 would be `rdoq` -- four to five launches of different kernels per step, none of them the step's longest
-        dom = max(ktimes, key=lambda k: ktimes[k] / kcount[k])
-        # roofline of the dominant launch group.  HBM: `achieved` counts UNIQUE algorithmic bytes -- SURVEY 8(d)'s operands once +
-        # results once per call, except where the calls of one search overlap (sad4: the box of a search's candidates + its source block once per run + 16 B per
-        # call; the per-call figure, which counts every reference sample ~112 times, is kept beside it as `operand_bytes_per_step`), so frac <= 1 by construction
-        # and comparable with `traffic`.  VALU: wavefront-level vector instructions (SQ_INSTS_VALU of a --pmc pass of this run) / duration against the issue peak.
-        unique = dict(kbytes)
-        if dom == "sad4":
-            unique["sad4"] = wl.sad4_unique_bytes()
-        ach = unique[dom] / (ktimes[dom] * 1e-3) / 1e9
-        total_bytes = sum(kbytes[k] for k in ktimes)
-        traffic, traffic_source, valu = None, None, None
-        if world == 1 and not (args.pcie or args.skip or args.no_graph) and args.min_seconds != 0:
-            c = counters_in_run(args, dom, wl.S, also=("rdoq",) if dom != "rdoq" and "rdoq" in ktimes else ())
-            if "FETCH_SIZE" in c and "WRITE_SIZE" in c:
-                traffic = round(c["FETCH_SIZE"] + c["WRITE_SIZE"])
-                traffic_source = ("measured in this run, bytes PER STEP (the unit of algorithmic_bytes_per_step): rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE, one "
-                                  "counter per pass, no trace domain) over a child run of exactly two steps of the same workload; FETCH_SIZE x2 per the gfx950 note; "
-                                  "summed over every launch of the group's kernels, divided by the steps")
-            if "SQ_INSTS_VALU" in c:
-                insts = c["SQ_INSTS_VALU"]
-                rate = insts / (ktimes[dom] * 1e-3) / 1e9
-                valu = {"insts_per_step": round(insts), "achieved": round(rate, 2), "peak": VALU_PEAK_GINST, "unit": "G wavefront-instructions/s",
-                        "frac": round(rate / VALU_PEAK_GINST, 5)}
-        if traffic is None:
-            traffic = hbm_traffic_from_profiles(dom, wl.S)
-            if traffic is not None:
-                traffic *= kcount[dom]      # the committed summary is per launch: times the group's launches per step (kernels of unequal size: approximate)
-            traffic_source = ("profiles/r*_hbm_traffic.csv (mean per launch x launches per step: approximate): separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this bench (profiles/collect.sh), "
-                              "FETCH_SIZE x2 per the gfx950 note; not re-measured in this run (rocprofv3 not on PATH, --traffic 0, or a diagnostic run)")
-        # the launch group furthest below any roofline is in the line too: `rdoq` -- several kernels of dependent decision chains per step
-        worst = None
-        if "rdoq" in ktimes and dom != "rdoq":
-            wc = (c.get("also", {}).get("rdoq", {}) if world == 1 and not (args.pcie or args.skip or args.no_graph) and args.min_seconds != 0 else {})      # (`c`: the counter passes above)
-            wa = kbytes["rdoq"] / (ktimes["rdoq"] * 1e-3) / 1e9
-            worst = {"bound": "hbm", "kernel": "rdoq", "achieved": round(wa, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(wa / HBM_PEAK_GBS, 5),
-                     "traffic": round(wc["FETCH_SIZE"] + wc["WRITE_SIZE"]) if "FETCH_SIZE" in wc and "WRITE_SIZE" in wc else None,
-                     "group_ms": round(ktimes["rdoq"], 5), "launches_per_step": kcount["rdoq"], "algorithmic_bytes_per_step": kbytes["rdoq"]}
-            if "SQ_INSTS_VALU" in wc:
-                wr = wc["SQ_INSTS_VALU"] / (ktimes["rdoq"] * 1e-3) / 1e9
-                worst["valu"] = {"insts_per_step": round(wc["SQ_INSTS_VALU"]), "achieved": round(wr, 2), "peak": VALU_PEAK_GINST, "frac": round(wr / VALU_PEAK_GINST, 5)}
         ms_step = elapsed / args.steps * 1e3
+        figures = kernel_figures(args, dev, wl, world, ms_step) if args.full else {}
         mixname = ("random-access QP%d speed=medium B-frame, MEASURED call mix of the reference encoder on this clip generator (profiles/r04_reference_call_mix_1080p.json: "
                    "call counts x %.2f by CTU count; measured block sizes, phase classes, DCT / DST split)" % (args.qp, ((w + 63) // 64) * ((h + 63) // 64) / 510.0)
                    if args.mix == "ra" else "all-intra QP%d speed=fast call mix (SURVEY A.1 per-CTU intra / TU counts, havoc_quantize in the chain)" % args.qp)
@@ -1902,23 +1936,7 @@ def main():
             "timing": {"timed_blocks": len(blocks), "block_seconds_median": round(blk, 6), "block_seconds_min": round(min(blocks), 6),
                        "block_seconds_max": round(max(blocks), 6), "seconds_measured": round(sum(blocks), 4),
                        "note": f"each block = exactly {args.steps} steps between barrier + synchronize; ms_per_step and value are the MEDIAN block"},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(ach, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(ach / HBM_PEAK_GBS, 5), "traffic": traffic,
-                         "traffic_source": traffic_source,
-                         "launch_ms": round(ktimes[dom] / kcount[dom], 5), "launches_per_step": kcount[dom],
-                         "algorithmic_bytes_per_step": unique[dom], "operand_bytes_per_step": kbytes[dom],
-                         "valu": valu, "valu_busy_pct": valu_busy_from_profiles(dom, wl.S),
-                         "note": ("achieved = unique algorithmic bytes / the group's isolated HIP-event time.  The group is not HBM-bound: its operands are cache- and LDS-resident "
-                                  "and what bounds it is instruction issue along short dependent chains -- `valu` is the instruction roofline (SQ_INSTS_VALU / time against "
-                                  "256 CUs x 4 SIMDs x 2.4 GHz / 2 cycles per wave64 instruction); `traffic` / `algorithmic_bytes_per_step` says how close the kernel is to "
-                                  "touching every byte once")},
-            "roofline_worst_group": worst,
-            # operand_gbs: the per-CALL operand bytes of SURVEY 8(d) over the step time -- NOT an HBM figure (the calls of a search name the same reference samples ~112 times and
-            # the operands are cache- and LDS-resident: it can exceed the HBM peak); the HBM statement is `roofline` (unique bytes, measured traffic)
-            "whole_step": {"operand_bytes": total_bytes, "operand_gbs": round(total_bytes / (ms_step * 1e-3) / 1e9, 2),
-                           "kernel_ms": {k: round(v, 4) for k, v in sorted(ktimes.items(), key=lambda kv: -kv[1])},
-                           "kernel_gbs": {k: round(kbytes[k] / (v * 1e-3) / 1e9, 1) for k, v in ktimes.items()}},
-            "checksum": dev.checksum(),
+            **figures,
         }
         if dumped is not None:
             out["outputs_dumped"] = {"dir": args.dump_outputs, "elements_written_of_buffer": dumped}
@@ -1940,8 +1958,9 @@ def main():
                              "kernels) -- not the benchmark metric")
         if args.skip:
             out["metric"] = "DIAGNOSTIC (launch groups skipped: " + args.skip + ") -- not the benchmark metric"
-        plain = world == 1 and pipe is None and not (args.pcie or args.skip or args.no_graph)
-        if plain and args.extra_4k and args.res == "1920x1080" and args.mix == "ra":
+        # the side measurements of --full around the undiagnostic single-GPU step
+        extras = args.full and world == 1 and pipe is None and not (args.pcie or args.skip or args.no_graph)
+        if extras and args.extra_4k and args.res == "1920x1080" and args.mix == "ra":
             # BASELINE.json configs[2] and [3] (the resolution the north star's target is quoted on, 8- and 10-bit), same code, fewer steps
             for xbd, xqp, label in ((8, 27, "3840x2160 8-bit random-access QP27 speed=medium (BASELINE.json configs[2])"),
                                     (10, 27, "3840x2160 10-bit Main10 random-access QP27 speed=medium (BASELINE.json configs[3])"),
@@ -1981,7 +2000,7 @@ def main():
                         "steps": ksteps, "timed_blocks": len(yb)}
                 except Exception as e:
                     out.setdefault("extra", {})["rdoq0_error"] = repr(e)
-        if plain and args.mix == "ra":
+        if extras and args.mix == "ra":
             # the same step with ONE picture in flight, a synchronisation after every picture: the latency a caller sees that needs a picture's
             # results before it can issue the next one
             try:
@@ -1998,7 +2017,7 @@ def main():
                     "launches_per_picture": len(dev.launches)}
             except Exception as e:
                 out.setdefault("extra", {})["one_in_flight_error"] = repr(e)
-        if plain and args.decisions and args.mix == "ra":
+        if extras and args.decisions and args.mix == "ra":
             # the decision-driven path: what the batches cost when decisions sit between them
             decision_walk = early.get("walk")
             for label, r in early.get("paths", {}).items():
@@ -2007,9 +2026,9 @@ def main():
                     r["ratio_note"] = ("`value` is one picture's primitive calls as ideal whole-frame batches (no decision between launches); this is the "
                                        "same kernels driven by decisions in an order a bit-exact encoder could issue them")
                 out.setdefault("extra", {})[label] = r
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, dev)
-            if plain and args.decisions and args.mix == "ra" and out["cpu_baseline"] is not None:
+            if extras and args.decisions and args.mix == "ra" and out["cpu_baseline"] is not None:
                 out["cpu_baseline"]["decision_walk"] = decision_walk
                 try:
                     enc = cpu_reference_encoder(args)
@@ -2028,9 +2047,10 @@ def main():
                 except Exception as e:
                     out["cpu_baseline"]["hooked_encoder"] = {"error": repr(e)}
         red = parity_problems(out)
-        out["parity"] = "red" if red else "green"
-        if red:
-            out["parity_problems"] = red
+        if args.full:      # (a plain run compares nothing with the reference, so it states no parity)
+            out["parity"] = "red" if red else "green"
+            if red:
+                out["parity_problems"] = red
         short = compact_line(out, args)
         line = json.dumps(short)
         for drop in ("poc_checksums", "whole_step", "extra", "timing"):      # the line must stay parseable by the driver whatever a run adds to it: shed the least needed first

@@ -7,13 +7,13 @@
 # Pass 1: rocprofv3 --kernel-trace --stats with one lane and no graph, so each kernel's duration is its isolated one
 #         (the figure bench.py's roofline.achieved is built from).  Pass 2: the same with the default 8 lanes + graph
 #         (durations overlap; kept to show the overlap, not for the roofline).  Passes 3/4: PMC counters, one counter
-#         per pass and no trace domains beside them.  Pass 5: the plain bench line with the CPU baseline.
+#         per pass and no trace domains beside them.  Pass 5: the --full bench line with the CPU baseline.
 tag=${1:-r05}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py --no-cpu-baseline --extra-4k 0 --decisions 0 --min-seconds 0"   # profiled runs: one timed block, no side measurements
+B="python $R/bench.py --full --no-cpu-baseline --extra-4k 0 --decisions 0 --min-seconds 0"   # profiled runs: one timed block, no side measurements
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${tag}_serial -- $B --steps 10 --warmup 2 --lanes 1 --no-graph > $O/${tag}_serial_bench.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${tag}_overlap8 -- $B --steps 10 --warmup 2 > $O/${tag}_overlap8_bench.log 2>&1
 timeout 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/${tag}_fetch -- $B --steps 2 --warmup 1 --kernel-reps 1 > /dev/null 2>&1
@@ -37,7 +37,7 @@ if f:
     st.to_csv("$O/${tag}_kernel_stats_overlap8.csv", index=False)
 PY
 timeout 120 python profiles/rdoq_bench.py 20 > $O/${tag}_rdoq_isolated.json 2>/dev/null
-timeout 400 python bench.py 2> $O/${tag}_bench.err | tail -1 > $O/${tag}_bench.json
+timeout 400 python bench.py --full 2> $O/${tag}_bench.err | tail -1 > $O/${tag}_bench.json
 tail -1 $O/${tag}_serial_bench.log | cut -c1-400
 tail -1 $O/${tag}_overlap8_bench.log | cut -c1-400
 cat $O/${tag}_bench.json

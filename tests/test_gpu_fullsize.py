@@ -294,7 +294,7 @@ def test_merged_prediction_launches_equal_the_per_class_launches(hv):
 
 
 def test_bench_line_contract():
-    """`python bench.py` prints ONE JSON line carrying every field of the driver's contract (plus roofline and
+    """`python bench.py --full` prints ONE JSON line carrying every field of the driver's contract (plus roofline and
     cpu_baseline), with the values the contract fixes"""
     import json
     import os
@@ -302,7 +302,7 @@ def test_bench_line_contract():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     # --decisions 0: the decision-driven path (two more processes, ~40 s) has its own tests (test_decisions.py, test_search.py)
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "6", "--warmup", "2", "--tune", "4", "--kernel-reps", "1", "--decisions", "0"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "6", "--warmup", "2", "--tune", "4", "--kernel-reps", "1", "--decisions", "0"],
                          capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -328,6 +328,34 @@ def test_bench_line_contract():
     if cb is not None:   # None only when oracle/_ref was never built
         assert set(("value", "unit", "cores", "kind", "sample")) <= set(cb) and cb["kind"] == "reference" and cb["cores"] >= 1
         assert cb["parity_vs_reference"]["mismatches"] == 0
+
+
+def test_plain_bench_line_is_the_headline_alone(tmp_path):
+    """a plain `python bench.py --gpus 1 --steps K --warmup W` sets up, warms up, times exactly K steps and prints the contract's keys; nothing that
+    --full adds (per-kernel times and roofline, other configurations, the decision-driven path, CPU baselines, parity) runs, so that the whole
+    process spends well under 30 s outside its steps"""
+    import json
+    import os
+    import subprocess
+    import sys
+    import time
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    t0 = time.perf_counter()
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--detail-out", str(tmp_path / "detail.json")],
+                         capture_output=True, text=True, timeout=300, cwd=root)
+    wall = time.perf_counter() - t0
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    r = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
+        assert k in r, k
+    assert r["n_gpus"] == 1 and r["steps"] == 20 and r["warmup"] == 5 and r["timing"]["timed_blocks"] == 1
+    assert r["unit"] == "frames/s" and r["higher_is_better"] is True and r["dtype"] == "u8"
+    assert abs(r["value"] - 1e3 / r["ms_per_step"]) / r["value"] < 0.01
+    for k in ("roofline", "roofline_worst_group", "whole_step", "checksum", "extra", "cpu_baseline", "parity"):
+        assert k not in r, k
+    assert wall - 25 * r["ms_per_step"] * 1e-3 < 30.0, wall
 
 
 @pytest.mark.gpu
