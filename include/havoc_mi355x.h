@@ -545,6 +545,46 @@ int havoc_mi355x_sao_estimate(havoc_mi355x_ctx *ctx, int S, int bitDepth, int32_
                               void *d_dst_y, void *d_dst_c, intptr_t stride_dst_y, intptr_t stride_dst_c,
                               const havoc_mi355x_sao_ctu *d_ctus, int nctus, void *d_work, size_t work_bytes, havoc_mi355x_sao_params *d_params);
 
+/* The final SAO parameters of a picture's CTUs: the last step of EncSao::rdSao (turing/EncSao.h:1017-1120), in one call on the context's
+ * stream (no host synchronisation, no allocation: capturable into a graph).  Per CTU in raster order, four candidates priced as
+ * rate + distortion x reciprocal_lambda_q16 (Cost = FixedPoint<int64_t, 16>; a context-coded bin costs measureEncodeDecision,
+ * Write.h:476-492, a bypass bin 1 << 16): the estimate of havoc_mi355x_sao_estimate (dist_sao), all off (dist_off; tried only when
+ * the luma or chroma estimate is not type 0), merge-up (when ry > 0) and merge-left (when rx > 0), each merge with the neighbour's
+ * FINAL parameters.  A later candidate wins only with a strictly lower cost.  The rates are Search<sao>::go's (Search.hpp:641-705):
+ * merge-up codes sao_merge_left_flag = 0 first when rx > 0; sao_offset_abs is truncated unary with cMax = (1 << (min(bitDepth, 10) - 5)) - 1;
+ * the second bin of sao_type_idx, the signs, the band position (5 bins) and the edge class (2 bins) are bypass; Cr is not priced
+ * at all (the reference's rate under-counts it).  After the choice the two contexts move with the bins the encoder writes.
+ *   Inputs: the planes, strides and CTU table given to havoc_mi355x_sao_estimate (raster order, ctus_x CTUs per row, nctus / ctus_x
+ * rows, 1 <= ctus_x <= 512) and what it wrote to d_params; the destination planes as it left them.  reciprocal_lambda_q16 as there.
+ * flags: bit 0 slice_sao_luma_flag, bit 1 slice_sao_chroma_flag (as given to the estimate), bit 2 entropy_coding_sync_enabled_flag
+ * (WPP: a row starts from the states after CTU (1, r - 1), or from the slice's when that CTU does not exist; without it a row starts
+ * where the row above ended).  ctx_sao_merge / ctx_sao_type: ContextModel::state (2 pStateIdx + valMps, turing/Cabac.cpp:26-37) of
+ * sao_merge_X_flag and sao_type_idx_X at the slice start.  One slice starting at CTU 0, one tile, 4:2:0.  With flags & 3 == 0 no sao()
+ * is coded (SyntaxCtu.hpp:40): every record is all off and the states do not move.
+ *   Outputs: one record per CTU, and the destination rewritten for every CTU whose final parameters differ from its estimate, so that it
+ * holds every CTU filtered with its final parameters (computeSaoDistortion's form).  A CTU record that the estimate reports off (odd
+ * or out-of-range size) is never written and takes part with distortion 0.
+ * d_work: havoc_mi355x_sao_decide_workspace(nctus) bytes of device scratch, 16-byte aligned, private to the call until it completes.
+ * The call waits inside the device on the row above (bounded waits); if one gives up, every record has decided = 0. */
+typedef struct {
+    havoc_mi355x_sao_component comp[2];   /* the final parameters; a type-0 component is all zeros (the reference's SaoCtuData keeps the
+                                             estimate's stale fields there, which nothing reads) */
+    int32_t merge_left, merge_up;    /* sao_merge_left_flag, sao_merge_up_flag */
+    int32_t dist;                    /* computeSaoDistortion with the final parameters */
+    int32_t source;                  /* the CTU whose estimate the final parameters are (merges followed to their origin); -1: all off */
+    uint8_t ctx_merge_before, ctx_type_before;   /* the two context states before this CTU's SAO syntax ... */
+    uint8_t ctx_merge_after, ctx_type_after;     /* ... and after it */
+    int32_t decided;                 /* 1; 0 when a wait inside the call gave up (then no record of the call is a decision) */
+    int32_t reserved[4];
+} havoc_mi355x_sao_decision; /* 128 bytes */
+size_t havoc_mi355x_sao_decide_workspace(int nctus);
+int havoc_mi355x_sao_decide(havoc_mi355x_ctx *ctx, int S, int bitDepth, int32_t reciprocal_lambda_q16, int flags,
+                            const void *d_src_y, const void *d_src_c, intptr_t stride_src_y, intptr_t stride_src_c,
+                            const void *d_rec_y, const void *d_rec_c, intptr_t stride_rec_y, intptr_t stride_rec_c,
+                            void *d_dst_y, void *d_dst_c, intptr_t stride_dst_y, intptr_t stride_dst_c,
+                            const havoc_mi355x_sao_ctu *d_ctus, int nctus, int ctus_x, const havoc_mi355x_sao_params *d_params,
+                            int ctx_sao_merge, int ctx_sao_type, void *d_work, size_t work_bytes, havoc_mi355x_sao_decision *d_decisions);
+
 /* ------------------------------------------------------------------------------------------------------- */
 /* rate-distortion optimised quantisation                                                 */
 /* ------------------------------------------------------------------------------------------------------- */

@@ -66,6 +66,10 @@ hipError_t launch_sao_filter(hipStream_t, int S, int bd, void *, long, const voi
 size_t sao_workspace_bytes(int nctus);
 hipError_t launch_sao_estimate(hipStream_t, int S, int bd, double lambda, int flags, const void *, const void *, long, long, const void *, const void *, long, long,
                                void *, void *, long, long, const void *, int, void *, void *);
+size_t sao_decide_workspace_bytes(int nctus);
+int sao_decide_max_row();
+hipError_t launch_sao_decide(hipStream_t, int S, int bd, long long lambda, int flags, const void *, const void *, long, long, const void *, const void *, long, long,
+                             void *, void *, long, long, const void *, int, int, const void *, int, int, void *, void *);
 hipError_t launch_quantize_inverse(hipStream_t, int16_t *, const int16_t *, const void *, int);
 hipError_t launch_quantize_reconstruct(hipStream_t, int log2, uint8_t *, long, const uint8_t *, long, const int16_t *, const void *, int);
 hipError_t launch_residual(hipStream_t, int S, int16_t *, long, const int32_t *, const void *, long, const void *, long, const void *, int);
@@ -88,6 +92,8 @@ static_assert(sizeof(havoc_mi355x_quant_job) == 32, "job ABI");
 static_assert(sizeof(havoc_mi355x_sao_ctu) == 64 && sizeof(havoc_mi355x_sao_component) == 44 && sizeof(havoc_mi355x_sao_params) == 128, "sao record ABI");
 static_assert(offsetof(havoc_mi355x_sao_params, dist_sao) == 88 && offsetof(havoc_mi355x_sao_params, ssd_sao) == 96 && offsetof(havoc_mi355x_sao_ctu, stat_src_cb) == 48,
               "sao record ABI");
+static_assert(sizeof(havoc_mi355x_sao_decision) == 128 && offsetof(havoc_mi355x_sao_decision, merge_left) == 88 &&
+              offsetof(havoc_mi355x_sao_decision, ctx_merge_before) == 104 && offsetof(havoc_mi355x_sao_decision, decided) == 108, "sao record ABI");
 static_assert(sizeof(havoc_mi355x_intra_mpm) == 40 && sizeof(havoc_mi355x_intra_choice) == 40, "job ABI");
 
 #include "ctx.h"
@@ -936,6 +942,31 @@ int havoc_mi355x_sao_estimate(havoc_mi355x_ctx *ctx, int S, int bitDepth, int32_
     return check(launch_sao_estimate(LS(ctx), S, bitDepth, lambda, flags, d_src_y, d_src_c, stride_src_y, stride_src_c, d_rec_y, d_rec_c, stride_rec_y,
                                      stride_rec_c, d_dst_y, d_dst_c, stride_dst_y, stride_dst_c, d_ctus, nctus, d_work, d_params),
                  "sao_estimate");
+}
+
+size_t havoc_mi355x_sao_decide_workspace(int nctus) { return sao_decide_workspace_bytes(nctus); }
+
+int havoc_mi355x_sao_decide(havoc_mi355x_ctx *ctx, int S, int bitDepth, int32_t reciprocal_lambda_q16, int flags, const void *d_src_y, const void *d_src_c,
+                            intptr_t stride_src_y, intptr_t stride_src_c, const void *d_rec_y, const void *d_rec_c, intptr_t stride_rec_y, intptr_t stride_rec_c,
+                            void *d_dst_y, void *d_dst_c, intptr_t stride_dst_y, intptr_t stride_dst_c, const havoc_mi355x_sao_ctu *d_ctus, int nctus, int ctus_x,
+                            const havoc_mi355x_sao_params *d_params, int ctx_sao_merge, int ctx_sao_type, void *d_work, size_t work_bytes,
+                            havoc_mi355x_sao_decision *d_decisions)
+{
+    REQUIRE_CTX(); REQUIRE_S(); REQUIRE_BD(); REQUIRE(nctus >= 0, "nctus < 0");
+    REQUIRE(reciprocal_lambda_q16 > 0, "sao_decide: reciprocal_lambda_q16 must be > 0");
+    REQUIRE(flags >= 0 && flags <= 7, "sao_decide: flags = bit 0 luma, bit 1 chroma, bit 2 entropy_coding_sync_enabled_flag");
+    REQUIRE(ctus_x >= 1 && ctus_x <= sao_decide_max_row(), "sao_decide: ctus_x must be 1..512");
+    REQUIRE(nctus % ctus_x == 0, "sao_decide: nctus must be a whole number of rows of ctus_x CTUs");
+    REQUIRE(ctx_sao_merge >= 0 && ctx_sao_merge <= 127 && ctx_sao_type >= 0 && ctx_sao_type <= 127, "sao_decide: context states are 0..127");
+    REQUIRE(nctus == 0 || (d_src_y && d_src_c && d_rec_y && d_rec_c && d_dst_y && d_dst_c && d_ctus && d_params && d_decisions),
+            "sao_decide: null plane, CTU, parameter or decision pointer");
+    REQUIRE(d_dst_y != d_rec_y && d_dst_c != d_rec_c, "sao_decide: the filtered picture and the reconstruction must be different buffers");
+    REQUIRE(nctus == 0 || (d_work && work_bytes >= sao_decide_workspace_bytes(nctus) && (reinterpret_cast<uintptr_t>(d_work) & 15) == 0),
+            "sao_decide: workspace missing, misaligned or smaller than havoc_mi355x_sao_decide_workspace(nctus)");
+    return check(launch_sao_decide(LS(ctx), S, bitDepth, reciprocal_lambda_q16, flags, d_src_y, d_src_c, stride_src_y, stride_src_c, d_rec_y, d_rec_c,
+                                   stride_rec_y, stride_rec_c, d_dst_y, d_dst_c, stride_dst_y, stride_dst_c, d_ctus, nctus, ctus_x, d_params, ctx_sao_merge,
+                                   ctx_sao_type, d_work, d_decisions),
+                 "sao_decide");
 }
 
 int havoc_mi355x_tu_forward_scan(havoc_mi355x_ctx *ctx, int S, int bitDepth, int log2TrafoSize, int16_t *d_coeffs, const void *d_src, intptr_t stride_src,

@@ -12,7 +12,7 @@
 //
 // The double arithmetic must round where the reference's x86-64 build rounds: no fused multiply-add (`deltaD + lambda * rate` is
 // two roundings there), sums in the reference's order, divisions in double (v_div_scale/fmas/fixup: IEEE).
-#include "common.h"
+#include "sao_ctu.h"
 
 #pragma clang fp contract(off)
 
@@ -20,13 +20,8 @@ namespace havoc_gpu {
 
 namespace {
 
-struct SaoCtu { int32_t src_y, src_cb, src_cr, rec_y, rec_cb, rec_cr, dst_y, dst_cb, dst_cr, w, h, reserved, stat_src_cb, stat_src_cr, stat_rec_cb, stat_rec_cr; };
-struct SaoComp { int32_t type, eo_class, band_position, offset_abs[4], offset_sign[4]; };
-struct SaoParams { SaoComp comp[2]; int32_t dist_sao, dist_off; uint32_t ssd_sao[3], ssd_off[3]; int32_t reserved[2]; };
 struct StatsJob { int32_t src_off, rec_off, w, h; };
 struct ChromaJob { int32_t src_u, src_v, rec_u, rec_v, w, h, reserved[2]; };
-static_assert(sizeof(SaoCtu) == sizeof(havoc_mi355x_sao_ctu) && sizeof(SaoCtu) == 64, "sao ctu layout");
-static_assert(sizeof(SaoParams) == sizeof(havoc_mi355x_sao_params) && sizeof(SaoParams) == 128, "sao params layout");
 static_assert(sizeof(StatsJob) == sizeof(havoc_mi355x_sao_stats_job) && sizeof(ChromaJob) == sizeof(havoc_mi355x_sao_chroma_job), "sao job layout");
 
 // the workspace: per CTU the statistics rows of kernels_sao.hip (Y 105, Cb 105, Cr 105, joint chroma bands 65 int64) and the jobs
@@ -48,9 +43,6 @@ __host__ __device__ inline Work work_of(void *base, int n)
     w.jobB = reinterpret_cast<ChromaJob *>(w.jobC + 2L * n);
     return w;
 }
-
-// a CTU the kernels can measure: luma 8..64 even (chroma 4..32); any other record is reported off and left alone
-__device__ __forceinline__ bool ctu_ok(const SaoCtu &c) { return c.w >= 8 && c.h >= 8 && c.w <= 64 && c.h <= 64 && !(c.w & 1) && !(c.h & 1); }
 
 __global__ __launch_bounds__(256) void k_sao_est_jobs(const SaoCtu *__restrict__ ctus, int n, Work wk)
 {
@@ -171,14 +163,6 @@ __device__ void decide(DecideLds &L, SaoComp &out, int lane, int bd, double lamb
     }
 }
 
-__device__ __forceinline__ int sign3(int v) { return (v > 0) - (v < 0); }
-
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
-{
-    for (int m = 32; m >= 1; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m, 64);
-    return v;
-}
-
 template <int S>
 __global__ __launch_bounds__(256) void k_sao_decide(const SaoCtu *__restrict__ ctus, Work wk, int bd, double lambda, int flags,
                                                     const char *__restrict__ srcY, const char *__restrict__ srcC, long ssy, long ssc,
@@ -229,58 +213,11 @@ __global__ __launch_bounds__(256) void k_sao_decide(const SaoCtu *__restrict__ c
     __syncthreads();
     if (active) decide(L[wave], comp[wave], lane, bd, lambda, wave ? 4 : 1);
     __syncthreads();
-    if (tid < 64)
-    {
-        // LoopFilter.h:134-160 SaoOffsetVal (edge signs + + - -, band signs from sao_offset_sign); the 32-entry band table
-        const int k = tid & 31, ci = tid >> 5;
-        const SaoComp &p = comp[ci];
-        const int sh = bd - min(bd, 10);
-        int v = 0;
-        if (p.type == 1)
-        {
-            const int j = (k - p.band_position) & 31;
-            if (j < 4) v = (p.offset_sign[j] ? -1 : 1) * p.offset_abs[j] << sh;
-        }
-        else if (p.type == 2 && k >= 1 && k <= 4)
-            v = (k <= 2 ? 1 : -1) * p.offset_abs[k - 1] << sh;
-        table[ci][k] = (int16_t)v;
-    }
+    sao_offset_table(table, comp, tid, bd);
     __syncthreads();
     // apply and measure (EncSao.h:861-945): Y, Cb, Cr; EncSao::ssd accumulates in uint32
     uint32_t acc[6] = { 0, 0, 0, 0, 0, 0 };
-    const int mx = (1 << bd) - 1;
-    for (int plane = 0; plane < 3; ++plane)
-    {
-        const int ci = plane ? 1 : 0, type = comp[ci].type, e = comp[ci].eo_class & 3;
-        const int bw = plane ? c.w >> 1 : c.w, bh = plane ? c.h >> 1 : c.h;
-        const long ss = plane ? ssc : ssy, rs = plane ? rsc : rsy, ds = plane ? dsc : dsy;
-        const T *src = reinterpret_cast<const T *>(plane ? srcC : srcY) + (plane == 0 ? c.src_y : plane == 1 ? c.src_cb : c.src_cr);
-        const T *rec = reinterpret_cast<const T *>(plane ? recC : recY) + (plane == 0 ? c.rec_y : plane == 1 ? c.rec_cb : c.rec_cr);
-        T *dst = reinterpret_cast<T *>(plane ? dstC : dstY) + (plane == 0 ? c.dst_y : plane == 1 ? c.dst_cb : c.dst_cr);
-        // neighbours of the edge class (sao.cpp:63-73): horizontal, vertical, 135 degrees, 45 degrees
-        const long n0 = (e == 0 ? 0 : -1) * rs + (e == 1 ? 0 : (e == 3 ? 1 : -1));
-        const int16_t *tb = table[ci];
-        for (int k = tid; k < bw * bh; k += 256)
-        {
-            const int y = k / bw, x = k - y * bw;
-            const T *r = rec + y * rs + x;
-            const int cv = r[0];
-            int v = cv;
-            if (type == 1)
-                v = cv + tb[cv >> (bd - 5)];
-            else if (type == 2)
-            {
-                int idx = 2 + sign3(cv - (int)r[n0]) + sign3(cv - (int)r[-n0]);
-                idx = idx > 2 ? idx : (idx == 2 ? 0 : idx + 1);
-                v = cv + tb[idx];
-            }
-            v = min(max(v, 0), mx);
-            dst[y * ds + x] = (T)v;
-            const int s = src[y * ss + x], d1 = s - v, d0 = s - cv;
-            acc[2 * plane] += (uint32_t)(d1 * d1);
-            acc[2 * plane + 1] += (uint32_t)(d0 * d0);
-        }
-    }
+    sao_filter_ctu<T, true>(c, comp, table, bd, srcY, srcC, ssy, ssc, recY, recC, rsy, rsc, dstY, dstC, dsy, dsc, acc);
 #pragma unroll
     for (int k = 0; k < 6; ++k)
     {

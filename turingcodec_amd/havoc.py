@@ -131,6 +131,8 @@ def _load():
         "sao_filter": [_vp, _i, _i, _vp, _ip, _vp, _ip, _vp, _i],
         "sao_band_chroma": [_vp, _i, _i, _vp, _ip, _vp, _ip, _vp, _i, _vp],
         "sao_estimate": [_vp, _i, _i, C.c_int32, _i, _vp, _vp, _ip, _ip, _vp, _vp, _ip, _ip, _vp, _vp, _ip, _ip, _vp, _i, _vp, C.c_size_t, _vp],
+        "sao_decide": [_vp, _i, _i, C.c_int32, _i, _vp, _vp, _ip, _ip, _vp, _vp, _ip, _ip, _vp, _vp, _ip, _ip, _vp, _i, _i, _vp, _i, _i, _vp, C.c_size_t,
+                       _vp],
     }
     L.havoc_mi355x_rdoq_lambda.argtypes = [C.c_double, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.havoc_mi355x_rdoq_lambda.restype = None
@@ -138,6 +140,8 @@ def _load():
     L.havoc_mi355x_rdoq_workspace.restype = C.c_size_t
     L.havoc_mi355x_sao_workspace.argtypes = [_i]
     L.havoc_mi355x_sao_workspace.restype = C.c_size_t
+    L.havoc_mi355x_sao_decide_workspace.argtypes = [_i]
+    L.havoc_mi355x_sao_decide_workspace.restype = C.c_size_t
     L.havoc_mi355x_search_workspace.argtypes = [_i, _i]
     L.havoc_mi355x_search_workspace.restype = C.c_size_t
     for name, args in sig.items():
@@ -151,7 +155,7 @@ def exported_symbols():
     """names the C ABI must export (checked against include/havoc_mi355x.h by the CPU tests)"""
     _, names = _load()
     return ["havoc_mi355x_" + n for n in names] + ["havoc_mi355x_last_error", "havoc_mi355x_version", "havoc_mi355x_rdoq_lambda", "havoc_mi355x_rdoq_workspace",
-                                                "havoc_mi355x_search_workspace", "havoc_mi355x_sao_workspace"]
+                                                "havoc_mi355x_search_workspace", "havoc_mi355x_sao_workspace", "havoc_mi355x_sao_decide_workspace"]
 
 
 # one havoc_mi355x_cell (include/havoc_mi355x.h), 16 bytes: a 4x4 luma cell of a picture's block structure
@@ -175,6 +179,25 @@ SAO_COMPONENT_DT = np.dtype([("type", "<i4"), ("eo_class", "<i4"), ("band_positi
 SAO_PARAMS_DT = np.dtype([("comp", SAO_COMPONENT_DT, 2), ("dist_sao", "<i4"), ("dist_off", "<i4"), ("ssd_sao", "<u4", 3), ("ssd_off", "<u4", 3),
                           ("reserved", "<i4", 2)])
 assert SAO_COMPONENT_DT.itemsize == 44 and SAO_PARAMS_DT.itemsize == 128
+
+# one havoc_mi355x_sao_decision (include/havoc_mi355x.h), 128 bytes: a CTU's final SAO parameters, merge flags, distortion and the
+# states of the contexts sao_merge_X_flag and sao_type_idx_X before and after its SAO syntax
+SAO_DECISION_DT = np.dtype([("comp", SAO_COMPONENT_DT, 2), ("merge_left", "<i4"), ("merge_up", "<i4"), ("dist", "<i4"), ("source", "<i4"),
+                            ("ctx_merge_before", "u1"), ("ctx_type_before", "u1"), ("ctx_merge_after", "u1"), ("ctx_type_after", "u1"),
+                            ("decided", "<i4"), ("reserved", "<i4", 4)])
+assert SAO_DECISION_DT.itemsize == 128
+
+
+def sao_context_init(slice_qp, init_type):
+    """-> (state of sao_merge_X_flag, state of sao_type_idx_X) at the start of a slice: H.265 9.3.2.2 with the initValues of Tables 9-5 /
+    9-6 (sao_merge: 153 for every initType; sao_type_idx: 200, 185, 160), as ContextModel::state = 2 pStateIdx + valMps"""
+    assert init_type in (0, 1, 2)
+
+    def state(init_value):
+        m, n = (init_value >> 4) * 5 - 45, ((init_value & 15) << 3) - 16
+        pre = min(max(1, ((m * min(max(0, slice_qp), 51)) >> 4) + n), 126)
+        return 2 * (pre - 64) + 1 if pre >= 64 else 2 * (63 - pre)
+    return state(153), state((200, 185, 160)[init_type])
 
 
 def sao_layout(width, height, pad=8):
@@ -670,6 +693,44 @@ class Havoc:
         self.sao_estimate_d(bd, lambda_q16, flags, sy, sc, stride_y, stride_c, ry, rc, stride_y, stride_c, dy, dc, stride_y, stride_c, d_ctus,
                             self.sao_workspace(len(ctus)), params)
         return self.down(params, np.uint8).view(SAO_PARAMS_DT), self.down(dy, rec_y.dtype), self.down(dc, rec_c.dtype)
+
+    def sao_decide_workspace(self, nctus):
+        """device scratch for one sao_decide call over `nctus` CTUs (an int64 tensor: 16-byte aligned)"""
+        n = int(self.L.havoc_mi355x_sao_decide_workspace(int(nctus)))
+        with self.torch.cuda.stream(self.tstream):
+            return self.torch.zeros((n + 7) // 8 + 2, dtype=self.torch.int64, device=self.device)
+
+    def sao_decide_d(self, bd, lambda_q16, flags, src_y, src_c, ssy, ssc, rec_y, rec_c, rsy, rsc, dst_y, dst_c, dsy, dsc, ctus, ctus_x, params, ctx_merge,
+                     ctx_type, work, decisions):
+        """device level: ctus = uint8 tensor of SAO_CTU_DT records, params = what sao_estimate_d wrote for them, decisions = uint8 tensor of as
+        many SAO_DECISION_DT records; no synchronisation and no allocation (graph capture).  The caller checks `decided` after its own
+        synchronisation: 0 means a wait inside the call gave up."""
+        self._ck(self.L.havoc_mi355x_sao_decide(self.h, self._S(src_y), bd, int(lambda_q16), int(flags), _ptr(src_y), _ptr(src_c), ssy, ssc,
+                                                _ptr(rec_y), _ptr(rec_c), rsy, rsc, _ptr(dst_y), _ptr(dst_c), dsy, dsc, _ptr(ctus),
+                                                ctus.numel() // SAO_CTU_DT.itemsize, int(ctus_x), _ptr(params), int(ctx_merge), int(ctx_type), _ptr(work),
+                                                work.numel() * 8, _ptr(decisions)))
+
+    def sao_decide(self, bd, lambda_q16, src_y, src_c, rec_y, rec_c, stride_y, stride_c, ctus, ctus_x, ctx_merge, ctx_type, flags=3):
+        """numpy level: sao_estimate, then the merge / off decision of every CTU of `ctus` (SAO_CTU_DT in raster order, `ctus_x` per row; one
+        layout for source, reconstruction and destination, e.g. sao_ctu_table); flags bit 2 = WPP; ctx_merge / ctx_type: the slice's initial
+        context states (sao_context_init).  -> (SAO_DECISION_DT records, SAO_PARAMS_DT estimate records, filtered luma plane, filtered chroma
+        plane with the final parameters); raises HavocError if a wait inside the call gave up."""
+        ctus = np.ascontiguousarray(ctus, SAO_CTU_DT)
+        torch = self.torch
+        sy, sc, ry, rc = self.up(src_y), self.up(src_c), self.up(rec_y), self.up(rec_c)
+        with torch.cuda.stream(self.tstream):
+            dy, dc = ry.clone(), rc.clone()
+            d_ctus = torch.from_numpy(ctus.view(np.uint8).reshape(-1)).to(self.device)
+            params = torch.zeros(len(ctus) * SAO_PARAMS_DT.itemsize, dtype=torch.uint8, device=self.device)
+            decisions = torch.zeros(len(ctus) * SAO_DECISION_DT.itemsize, dtype=torch.uint8, device=self.device)
+        self.sao_estimate_d(bd, lambda_q16, flags & 3, sy, sc, stride_y, stride_c, ry, rc, stride_y, stride_c, dy, dc, stride_y, stride_c, d_ctus,
+                            self.sao_workspace(len(ctus)), params)
+        self.sao_decide_d(bd, lambda_q16, flags, sy, sc, stride_y, stride_c, ry, rc, stride_y, stride_c, dy, dc, stride_y, stride_c, d_ctus, ctus_x,
+                          params, ctx_merge, ctx_type, self.sao_decide_workspace(len(ctus)), decisions)
+        dec = self.down(decisions, np.uint8).view(SAO_DECISION_DT)
+        if len(dec) and not (dec["decided"] == 1).all():
+            raise HavocError("sao_decide: a wait on the row above gave up; the decisions are not to be used")
+        return dec, self.down(params, np.uint8).view(SAO_PARAMS_DT), self.down(dy, rec_y.dtype), self.down(dc, rec_c.dtype)
 
     def rdoq_workspace(self, njobs):
         """device scratch for one rdoq launch of `njobs` blocks (an int64 tensor: 16-byte aligned)"""
