@@ -585,6 +585,39 @@ int havoc_mi355x_sao_decide(havoc_mi355x_ctx *ctx, int S, int bitDepth, int32_t 
                             const havoc_mi355x_sao_ctu *d_ctus, int nctus, int ctus_x, const havoc_mi355x_sao_params *d_params,
                             int ctx_sao_merge, int ctx_sao_type, void *d_work, size_t work_bytes, havoc_mi355x_sao_decision *d_decisions);
 
+/* In-loop SAO of a whole 4:2:0 picture, the pass a picture goes through before it becomes a reference: per CTU, what the encoder's
+ * TaskSao (turing/TaskSao.cpp:96-121) leaves in the picture -- LoopFilter::Picture::applySaoCTU -> filterBlockSao (turing/LoopFilter.h:
+ * 795-811, 886-1008) from a copy of the deblocked picture -- in one launch on the context's stream (no host synchronisation, no
+ * allocation: capturable into a graph).  Per CTU and colour component:
+ *   - the offsets of Ctu::set (LoopFilter.h:114-162): SaoOffsetVal[i + 1] = sign x sao_offset_abs << (bitDepth - min(bitDepth, 10)),
+ *     edge signs + + - -, SaoOffsetVal[0] = 0 (every band outside the four);
+ *   - band or edge filter (turing/sao.cpp:33-92), or a copy for type 0;
+ *   - restoreUnfilteredRegions (LoopFilter.h:850-877): the 8x8 luma / 4x4 chroma regions whose deblocking byte has the disabled bit;
+ *   - edge only: the undoT / undoL / undoR / undoB copies of filterBlockSao (LoopFilter.h:913-986) where a neighbour CTU is not
+ *     available, from the CTU's bounds and corner flags (processCtu, LoopFilter.h:475-537), right / bottom clamped to the CTU.
+ * d_rec_* / d_dst_*: sample (0, 0) of each plane; the destination must not overlap the source (filtering reads the deblocked
+ * neighbours, as the encoder's saoPicture copy does).  flags: bit 0 slice_sao_luma_flag, bit 1 slice_sao_chroma_flag; a component whose
+ * flag is 0 is copied.  d_decisions: one record per CTU in raster order, as havoc_mi355x_sao_decide writes them; comp[1] drives Cb and
+ * Cr; a record with decided == 0 is applied as all off.  d_bounds: one record per CTU in raster order, or NULL for one slice and one
+ * tile (the picture's edges only).  d_block_data: havoc_mi355x_deblock's (QpY << 1) | disabled bytes, row stride block_stride >=
+ * (width + 7) / 8, at least (height + 7) / 8 rows; NULL: no disabled regions.
+ * Writes every sample of [0, width) x [0, height) (luma) and [0, width / 2) x [0, height / 2) (Cb, Cr), and nothing outside: the
+ * reference filters chroma beyond the right and bottom picture edges (filterBlockSao clips chroma CTUs against the LUMA picture size,
+ * LoopFilter.h:895-897), into samples that padBlock overwrites before anything reads them (TaskSao.cpp:129-154).  Reads only inside
+ * the picture: a sample whose neighbour lies outside is always one the reference restores.
+ * EINVAL: overlapping planes, ctb_log2 outside 4..6, width / height not a positive multiple of 8, a bit depth outside 8..10 or not
+ * matching S, a null d_decisions, a block_stride too small. */
+typedef struct {
+    int32_t left, top, right, bottom; /* LoopFilter::Ctu's bounds in luma samples (processCtu, LoopFilter.h:476-535) */
+    int32_t corners;                  /* bit 0 topLeft, 1 topRight, 2 bottomLeft, 3 bottomRight */
+    int32_t reserved[3];
+} havoc_mi355x_sao_bounds; /* 32 bytes */
+int havoc_mi355x_sao_apply(havoc_mi355x_ctx *ctx, int S, int bitDepth, int flags, int width, int height, int ctb_log2,
+                           const void *d_rec_y, const void *d_rec_cb, const void *d_rec_cr, intptr_t stride_rec_y, intptr_t stride_rec_c,
+                           void *d_dst_y, void *d_dst_cb, void *d_dst_cr, intptr_t stride_dst_y, intptr_t stride_dst_c,
+                           const havoc_mi355x_sao_decision *d_decisions, const havoc_mi355x_sao_bounds *d_bounds,
+                           const int8_t *d_block_data, intptr_t block_stride);
+
 /* ------------------------------------------------------------------------------------------------------- */
 /* rate-distortion optimised quantisation                                                 */
 /* ------------------------------------------------------------------------------------------------------- */

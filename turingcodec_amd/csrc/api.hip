@@ -70,6 +70,8 @@ size_t sao_decide_workspace_bytes(int nctus);
 int sao_decide_max_row();
 hipError_t launch_sao_decide(hipStream_t, int S, int bd, long long lambda, int flags, const void *, const void *, long, long, const void *, const void *, long, long,
                              void *, void *, long, long, const void *, int, int, const void *, int, int, void *, void *);
+hipError_t launch_sao_apply(hipStream_t, int S, int bd, int flags, int width, int height, int log2, const void *, const void *, const void *, long, long,
+                            void *, void *, void *, long, long, const void *, const void *, const int8_t *, long);
 hipError_t launch_quantize_inverse(hipStream_t, int16_t *, const int16_t *, const void *, int);
 hipError_t launch_quantize_reconstruct(hipStream_t, int log2, uint8_t *, long, const uint8_t *, long, const int16_t *, const void *, int);
 hipError_t launch_residual(hipStream_t, int S, int16_t *, long, const int32_t *, const void *, long, const void *, long, const void *, int);
@@ -967,6 +969,44 @@ int havoc_mi355x_sao_decide(havoc_mi355x_ctx *ctx, int S, int bitDepth, int32_t 
                                    stride_rec_y, stride_rec_c, d_dst_y, d_dst_c, stride_dst_y, stride_dst_c, d_ctus, nctus, ctus_x, d_params, ctx_sao_merge,
                                    ctx_sao_type, d_work, d_decisions),
                  "sao_decide");
+}
+
+// [begin, end) of a plane's bytes: rows of `w` samples at stride `stride`
+static void plane_span(const void *p, intptr_t stride, int w, int h, int S, uintptr_t &b, uintptr_t &e)
+{
+    b = reinterpret_cast<uintptr_t>(p);
+    e = b + ((uintptr_t)(h - 1) * stride + w) * S;
+}
+
+int havoc_mi355x_sao_apply(havoc_mi355x_ctx *ctx, int S, int bitDepth, int flags, int width, int height, int ctb_log2, const void *d_rec_y,
+                           const void *d_rec_cb, const void *d_rec_cr, intptr_t stride_rec_y, intptr_t stride_rec_c, void *d_dst_y, void *d_dst_cb,
+                           void *d_dst_cr, intptr_t stride_dst_y, intptr_t stride_dst_c, const havoc_mi355x_sao_decision *d_decisions,
+                           const havoc_mi355x_sao_bounds *d_bounds, const int8_t *d_block_data, intptr_t block_stride)
+{
+    REQUIRE_CTX(); REQUIRE_S(); REQUIRE_BD();
+    REQUIRE(flags >= 0 && flags <= 3, "sao_apply: flags = bit 0 luma, bit 1 chroma");
+    REQUIRE(ctb_log2 >= 4 && ctb_log2 <= 6, "sao_apply: ctb_log2 must be 4..6");
+    REQUIRE(width >= 8 && height >= 8 && (width & 7) == 0 && (height & 7) == 0, "sao_apply: width / height must be positive multiples of 8");
+    REQUIRE(d_rec_y && d_rec_cb && d_rec_cr && d_dst_y && d_dst_cb && d_dst_cr && d_decisions, "sao_apply: null plane or decision pointer");
+    REQUIRE(stride_rec_y >= width && stride_dst_y >= width && stride_rec_c >= width / 2 && stride_dst_c >= width / 2, "sao_apply: a stride is shorter than a row");
+    REQUIRE(!d_block_data || block_stride >= (width + 7) / 8, "sao_apply: block_stride must be >= (width + 7) / 8");
+    const void *rec[3] = { d_rec_y, d_rec_cb, d_rec_cr }, *dst[3] = { d_dst_y, d_dst_cb, d_dst_cr };
+    uintptr_t rb[3], re[3], db[3], de[3];
+    for (int p = 0; p < 3; ++p)
+    {
+        const int w = p ? width / 2 : width, h = p ? height / 2 : height;
+        plane_span(rec[p], p ? stride_rec_c : stride_rec_y, w, h, S, rb[p], re[p]);
+        plane_span(dst[p], p ? stride_dst_c : stride_dst_y, w, h, S, db[p], de[p]);
+    }
+    for (int p = 0; p < 3; ++p)
+        for (int q = 0; q < 3; ++q)
+        {
+            REQUIRE(de[p] <= rb[q] || re[q] <= db[p], "sao_apply: a destination plane overlaps a source plane");
+            REQUIRE(p == q || de[p] <= db[q] || de[q] <= db[p], "sao_apply: destination planes overlap");
+        }
+    return check(launch_sao_apply(LS(ctx), S, bitDepth, flags, width, height, ctb_log2, d_rec_y, d_rec_cb, d_rec_cr, stride_rec_y, stride_rec_c, d_dst_y,
+                                  d_dst_cb, d_dst_cr, stride_dst_y, stride_dst_c, d_decisions, d_bounds, d_block_data, block_stride),
+                 "sao_apply");
 }
 
 int havoc_mi355x_tu_forward_scan(havoc_mi355x_ctx *ctx, int S, int bitDepth, int log2TrafoSize, int16_t *d_coeffs, const void *d_src, intptr_t stride_src,

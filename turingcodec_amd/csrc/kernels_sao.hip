@@ -9,7 +9,8 @@
 //                  against the two neighbours of the edge class); source and destination are different pictures, so every
 //                  sample is independent.
 // The parameter estimation from these statistics (EncSao.h:286-947) is kernels_sao_decide.hip, the merge / off choice
-// (EncSao.h:1017-1120) kernels_sao_merge.hip; the CTU availability rules (LoopFilter.h:886-1008) stay on the host.
+// (EncSao.h:1017-1120) kernels_sao_merge.hip; the in-loop pass with the CTU availability rules (LoopFilter.h:886-1008)
+// kernels_sao_apply.hip.
 //
 // One workgroup per job (a CTU of one colour component).  Statistics: a lane takes samples of the interior at stride 256, reads
 // the 3x3 neighbourhood through the cache; the 4 x 5 edge categories accumulate in registers (select on the category, wave

@@ -420,8 +420,12 @@ class DecisionPicture:
 
     PAD = 96
 
-    def __init__(self, hv, width, height, bit_depth=8, qp=32, seed=11, threads=16, frames=None, density=1.0, intra=True, search_on_device=True, distance=1):
+    def __init__(self, hv, width, height, bit_depth=8, qp=32, seed=11, threads=16, frames=None, density=1.0, intra=True, search_on_device=True, distance=1,
+                 sao=False):
         import torch
+        if sao and not search_on_device:
+            raise ValueError("sao=True needs the device route (search_on_device=True)")
+        self.sao = sao                                # in-loop SAO between deblocking and padding (sao_filter_inputs / sao_loop_filter)
         from . import havoc as hmod
         from . import workload
         self.hv, self.torch, self.hmod = hv, torch, hmod
@@ -753,6 +757,75 @@ class DecisionPicture:
         hv.deblock_d(bd, self.recon, self.origin, self.stride, self.d_chroma, 0, (self.H // 2) * (self.W // 2), self.W // 2, self.W, self.H, self.d_data, self.d_bs)
         hv.pad_block_d(self.recon, self.origin, self.W, self.H, self.stride, self.PAD)
 
+    # ---- in-loop SAO (sao=True): deblocked picture -> sao_estimate -> sao_decide -> sao_apply -> padded reference (turing/TaskSao.cpp:96-154) ---------------
+    def sao_filter_inputs(self, field):
+        """what the loop filter of a sao=True step reads: the transform-tree decisions, the block structure, the boundary strengths, and the chroma chain's
+        reconstruction (crecon).  Launches only."""
+        hv = self.hv
+        P = self.tree_decisions()
+        hv.block_cells_d(self.W, self.H, self.qp, 0, self.d_field, P["d_units"].view(-1, 4), P["d_out"], self.d_cells)
+        hv.derive_bs_d(self.d_cells, self.W // 4, self.W, self.H, self.d_data, self.d_bs)
+        self.chroma_chain(field)
+
+    def _sao_buffers(self):
+        """the deblocked copies, the scratch destination of the SAO decision, its records and workspaces and the CTU table over this picture's layout: source
+        luma at plane 0 of d_pic, source Cb / Cr at planes 0 / 3 of d_cpic; deblocked picture and destination in the layout of recon / crecon (Cr at cpe)"""
+        if hasattr(self, "deblocked"):
+            return
+        hv, torch, hmod = self.hv, self.torch, self.hmod
+        self.deblocked, self.cdeblocked = hv.zeros(self.pe, self.dt), hv.zeros(2 * self.cpe, self.dt)
+        self.sao_dst, self.csao_dst = hv.zeros(self.pe, self.dt), hv.zeros(2 * self.cpe, self.dt)
+        rows = []
+        c2 = self.PAD // 2
+        for y in range(0, self.H, 64):
+            for x in range(0, self.W, 64):
+                oy = (y + self.PAD) * self.stride + x + self.PAD
+                oc = (y // 2 + c2) * self.cstride + x // 2 + c2
+                w, h = min(64, self.W - x), min(64, self.H - y)
+                rows.append((oy, oc, 3 * self.cpe + oc, oy, oc, self.cpe + oc, oy, oc, self.cpe + oc, w, h, 0, oc, 3 * self.cpe + oc, oc, self.cpe + oc))
+        self.sao_ctus = np.array(rows, np.int32).view(hmod.SAO_CTU_DT).reshape(-1)
+        n = len(self.sao_ctus)
+        with torch.cuda.stream(hv.tstream):
+            self.d_sao_ctus = torch.from_numpy(self.sao_ctus.view(np.uint8).reshape(-1).copy()).to(hv.device)
+            self.d_sao_params = torch.zeros(n * hmod.SAO_PARAMS_DT.itemsize, dtype=torch.uint8, device=hv.device)
+            self.d_sao_decisions = torch.zeros(n * hmod.SAO_DECISION_DT.itemsize, dtype=torch.uint8, device=hv.device)
+        self.sao_work, self.sao_decide_work = hv.sao_workspace(n), hv.sao_decide_workspace(n)
+        self.sao_ctx = hmod.sao_context_init(self.qp, 2)          # a B slice
+
+    def sao_loop_filter(self):
+        """one deblocking call over the luma and the real chroma reconstruction; a copy of the deblocked planes padded by edge replication (the decision
+        filters one sample beyond the picture); sao_estimate -> sao_decide (WPP, the picture's lambda) into scratch planes; sao_apply from the deblocked
+        copy into recon / crecon; padding.  Launches only."""
+        self._sao_buffers()
+        hv, bd, W, H, c2 = self.hv, self.bd, self.W, self.H, self.PAD // 2
+        o, co, cs = self.origin, self.corigin, self.cstride
+        hv.deblock_d(bd, self.recon, o, self.stride, self.crecon, co, self.cpe + co, cs, W, H, self.d_data, self.d_bs)
+        # the copy: sao_apply with both slice flags 0 copies every picture sample
+        hv.sao_apply_d(bd, 0, W, H, 6, self.recon, o, self.crecon, co, self.cpe + co, self.stride, cs, self.deblocked, o, self.cdeblocked, co,
+                       self.cpe + co, self.stride, cs, self.d_sao_decisions)
+        hv.pad_block_d(self.deblocked, o, W, H, self.stride, self.PAD)
+        hv.pad_block_d(self.cdeblocked, co, W // 2, H // 2, cs, c2)
+        hv.pad_block_d(self.cdeblocked, self.cpe + co, W // 2, H // 2, cs, c2)
+        q16 = self.rqt_plan["rl_q16"]
+        sl = (self.stride, cs)
+        hv.sao_estimate_d(bd, q16, 3, self.d_pic, self.d_cpic, *sl, self.deblocked, self.cdeblocked, *sl, self.sao_dst, self.csao_dst, *sl, self.d_sao_ctus,
+                          self.sao_work, self.d_sao_params)
+        hv.sao_decide_d(bd, q16, 7, self.d_pic, self.d_cpic, *sl, self.deblocked, self.cdeblocked, *sl, self.sao_dst, self.csao_dst, *sl, self.d_sao_ctus,
+                        self.cx, self.d_sao_params, self.sao_ctx[0], self.sao_ctx[1], self.sao_decide_work, self.d_sao_decisions)
+        n64 = (W + 63) // 64 * 8 + 1
+        hv.sao_apply_d(bd, 3, W, H, 6, self.deblocked, o, self.cdeblocked, co, self.cpe + co, self.stride, cs, self.recon, o, self.crecon, co, self.cpe + co,
+                       self.stride, cs, self.d_sao_decisions, None, self.d_data, n64)
+        hv.pad_block_d(self.recon, o, W, H, self.stride, self.PAD)
+        hv.pad_block_d(self.crecon, co, W // 2, H // 2, cs, c2)
+        hv.pad_block_d(self.crecon, self.cpe + co, W // 2, H // 2, cs, c2)
+
+    @property
+    def sao_decisions(self):
+        """the SAO decisions of the last sao=True step (SAO_DECISION_DT per 64x64 CTU in raster order): downloaded when asked for"""
+        if getattr(self, "_sao_decisions", None) is None:
+            self._sao_decisions = self.hv.down(self.d_sao_decisions, np.uint8).view(self.hmod.SAO_DECISION_DT).copy()
+        return self._sao_decisions
+
     def tree_decisions(self):
         """the transform-tree part of tree_and_filter_on_device for self.units; returns the plan (its d_units / d_out are what the block structure is made from)"""
         hv, bd = self.hv, self.bd
@@ -893,8 +966,13 @@ class DecisionPicture:
         if self.search_on_device:
             # everything after the searches is a FIXED sequence of launches over device-resident tables (the decided field never leaves the device, the decisions
             # between the launches are kernels): recorded once into a HIP graph, one launch per picture, one wait at the end
-            self._rqt = self._cells = None
-            self._replayed("after the searches", lambda: (self.merge_candidates(field), self.predict(field), self.tree_and_filter_on_device(), self.chroma_chain(field)))
+            self._rqt = self._cells = self._sao_decisions = None
+            if self.sao:
+                self._replayed("after the searches", lambda: (self.merge_candidates(field), self.predict(field), self.sao_filter_inputs(field),
+                                                              self.sao_loop_filter()))
+            else:
+                self._replayed("after the searches", lambda: (self.merge_candidates(field), self.predict(field), self.tree_and_filter_on_device(),
+                                                              self.chroma_chain(field)))
             self.rqt_stats = RqtStats()
             self.rqt_stats.launches, self.rqt_stats.candidates = self.rqt_plan["launches"], 5 * len(self.units)
         else:
@@ -949,6 +1027,9 @@ class DecisionPicture:
         hv, torch, W, H = self.hv, self.torch, self.W, self.H
         if not self.search_on_device:
             raise ValueError("step_banded needs the device search")
+        if self.sao:
+            # SAO of band b reads the deblocked rows of band b + 1 (turing/TaskSao.cpp:46-56): not built
+            raise ValueError("step_banded does not run SAO: use step() with sao=True")
         views = self._band_views(band_ctu_rows, side)
         if make_phase_planes:
             self.phase_planes()

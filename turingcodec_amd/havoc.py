@@ -133,6 +133,7 @@ def _load():
         "sao_estimate": [_vp, _i, _i, C.c_int32, _i, _vp, _vp, _ip, _ip, _vp, _vp, _ip, _ip, _vp, _vp, _ip, _ip, _vp, _i, _vp, C.c_size_t, _vp],
         "sao_decide": [_vp, _i, _i, C.c_int32, _i, _vp, _vp, _ip, _ip, _vp, _vp, _ip, _ip, _vp, _vp, _ip, _ip, _vp, _i, _i, _vp, _i, _i, _vp, C.c_size_t,
                        _vp],
+        "sao_apply": [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _ip, _ip, _vp, _vp, _vp, _ip, _ip, _vp, _vp, _vp, _ip],
     }
     L.havoc_mi355x_rdoq_lambda.argtypes = [C.c_double, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.havoc_mi355x_rdoq_lambda.restype = None
@@ -186,6 +187,53 @@ SAO_DECISION_DT = np.dtype([("comp", SAO_COMPONENT_DT, 2), ("merge_left", "<i4")
                             ("ctx_merge_before", "u1"), ("ctx_type_before", "u1"), ("ctx_merge_after", "u1"), ("ctx_type_after", "u1"),
                             ("decided", "<i4"), ("reserved", "<i4", 4)])
 assert SAO_DECISION_DT.itemsize == 128
+
+# one havoc_mi355x_sao_bounds (include/havoc_mi355x.h), 32 bytes: LoopFilter::Ctu's bounds in luma samples and its corner flags
+SAO_BOUNDS_DT = np.dtype([("left", "<i4"), ("top", "<i4"), ("right", "<i4"), ("bottom", "<i4"), ("corners", "<i4"), ("reserved", "<i4", 3)])
+assert SAO_BOUNDS_DT.itemsize == 32
+SAO_CORNER_TL, SAO_CORNER_TR, SAO_CORNER_BL, SAO_CORNER_BR = 1, 2, 4, 8
+
+
+def sao_bounds_table(width, height, ctb_size, slice_starts=(0,), across_slices=(1,)):
+    """SAO_BOUNDS_DT records of every CTU in raster order, as LoopFilter::Picture::processCtu and neighbourCtuAvailable derive them
+    (turing/LoopFilter.h:462-537) for slices in raster order, one tile: slice s starts at CTU slice_starts[s] (ascending, the first 0) with
+    slice_loop_filter_across_slices_enabled_flag across_slices[s].  A neighbour is unavailable outside the picture, or when it precedes
+    the current CTU's slice and that slice's flag is 0.  A CTU's right / bottom and its bottomRight / bottomLeft are set by the LATER CTU,
+    with that CTU's flag."""
+    assert ctb_size in (16, 32, 64) and len(slice_starts) == len(across_slices) and slice_starts[0] == 0
+    assert all(a < b for a, b in zip(slice_starts, slice_starts[1:]))
+    cx, cy = -(-width // ctb_size), -(-height // ctb_size)
+    out = np.zeros(cx * cy, SAO_BOUNDS_DT)
+    slice_of = np.searchsorted(np.asarray(slice_starts), np.arange(cx * cy), side="right") - 1
+    for a in range(cx * cy):
+        rx, ry = a % cx, a // cx
+        start, across = slice_starts[slice_of[a]], across_slices[slice_of[a]]
+
+        def available(dx, dy):
+            if not (0 <= rx + dx < cx and 0 <= ry + dy < cy):
+                return False
+            return a + dx + dy * cx >= start or bool(across)
+
+        c = out[a]
+        c["left"], c["top"], c["right"], c["bottom"] = 0, 0, width, height
+        if not available(-1, 0):
+            c["left"] = rx * ctb_size
+            if rx:
+                out[a - 1]["right"] = rx * ctb_size
+        if not available(0, -1):
+            c["top"] = ry * ctb_size
+            if ry:
+                out[a - cx]["bottom"] = ry * ctb_size
+        corners = 0
+        tl, tr = available(-1, -1), available(1, -1)
+        corners |= SAO_CORNER_TL if tl else 0
+        if rx and ry:
+            out[a - 1 - cx]["corners"] = (out[a - 1 - cx]["corners"] & ~SAO_CORNER_BR) | (SAO_CORNER_BR if tl else 0)
+        corners |= SAO_CORNER_TR if tr else 0
+        if rx < cx - 1 and ry:
+            out[a + 1 - cx]["corners"] = (out[a + 1 - cx]["corners"] & ~SAO_CORNER_BL) | (SAO_CORNER_BL if tr else 0)
+        c["corners"] = corners        # bottomRight / bottomLeft false until a later CTU sets them
+    return out
 
 
 def sao_context_init(slice_qp, init_type):
@@ -731,6 +779,35 @@ class Havoc:
         if len(dec) and not (dec["decided"] == 1).all():
             raise HavocError("sao_decide: a wait on the row above gave up; the decisions are not to be used")
         return dec, self.down(params, np.uint8).view(SAO_PARAMS_DT), self.down(dy, rec_y.dtype), self.down(dc, rec_c.dtype)
+
+    def sao_apply_d(self, bd, flags, width, height, ctb_log2, rec_y, rec_y_off, rec_c, rec_cb_off, rec_cr_off, rsy, rsc, dst_y, dst_y_off, dst_c,
+                    dst_cb_off, dst_cr_off, dsy, dsc, decisions, bounds=None, block_data=None, block_stride=0):
+        """device level: the in-loop SAO of a picture from the deblocked planes (rec_*) into different ones (dst_*); *_off = element offset
+        of sample (0, 0) of each plane; decisions = uint8 tensor of SAO_DECISION_DT records in raster order; bounds = uint8 tensor of
+        SAO_BOUNDS_DT records or None (one slice); block_data = int8 tensor of deblocking bytes (row stride block_stride) or None.  No
+        synchronisation and no allocation (graph capture)."""
+        S = self._S(rec_y)
+        self._ck(self.L.havoc_mi355x_sao_apply(self.h, S, bd, int(flags), int(width), int(height), int(ctb_log2), rec_y.data_ptr() + rec_y_off * S,
+                                               rec_c.data_ptr() + rec_cb_off * S, rec_c.data_ptr() + rec_cr_off * S, rsy, rsc,
+                                               dst_y.data_ptr() + dst_y_off * S, dst_c.data_ptr() + dst_cb_off * S, dst_c.data_ptr() + dst_cr_off * S,
+                                               dsy, dsc, _ptr(decisions), _ptr(bounds), _ptr(block_data), int(block_stride)))
+
+    def sao_apply(self, bd, flags, ctb_log2, rec_y, rec_cb, rec_cr, decisions, bounds=None, block_data=None):
+        """numpy level: planes WITHOUT padding (2-D, stride = row length), decisions = SAO_DECISION_DT records in raster order, bounds =
+        SAO_BOUNDS_DT records (e.g. sao_bounds_table) or None, block_data = 2-D int8 deblocking bytes or None -> the three filtered planes"""
+        torch = self.torch
+        height, width = rec_y.shape
+        c = np.concatenate([rec_cb.ravel(), rec_cr.ravel()])
+        ry, rc = self.up(np.ascontiguousarray(rec_y).ravel()), self.up(c)
+        with torch.cuda.stream(self.tstream):
+            dy, dc = torch.zeros_like(ry), torch.zeros_like(rc)
+            d_dec = torch.from_numpy(np.ascontiguousarray(decisions, SAO_DECISION_DT).view(np.uint8).reshape(-1)).to(self.device)
+            d_bounds = None if bounds is None else torch.from_numpy(np.ascontiguousarray(bounds, SAO_BOUNDS_DT).view(np.uint8).reshape(-1)).to(self.device)
+            d_blk = None if block_data is None else torch.from_numpy(np.ascontiguousarray(block_data, np.int8).ravel()).to(self.device)
+        self.sao_apply_d(bd, flags, width, height, ctb_log2, ry, 0, rc, 0, rec_cb.size, width, width // 2, dy, 0, dc, 0, rec_cb.size, width,
+                         width // 2, d_dec, d_bounds, d_blk, 0 if block_data is None else block_data.shape[1])
+        o = self.down(dc, rec_cb.dtype)
+        return self.down(dy, rec_y.dtype).reshape(rec_y.shape), o[:rec_cb.size].reshape(rec_cb.shape), o[rec_cb.size:].reshape(rec_cr.shape)
 
     def rdoq_workspace(self, njobs):
         """device scratch for one rdoq launch of `njobs` blocks (an int64 tensor: 16-byte aligned)"""
