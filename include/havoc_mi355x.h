@@ -200,7 +200,12 @@ int havoc_mi355x_pad_block(havoc_mi355x_ctx *ctx, int S, void *d_plane, int64_t 
  * strengths and QPs -- the encoder's decisions (LoopFilter.h:480-737) -- come as the two arrays of LoopFilter::Block on its
  * grid of ((width + 63) / 64 * 8 + 1) x ((height + 63) / 64 * 8 + 1) regions: d_block_data[i] = (QpY << 1) | filter-disabled,
  * d_block_bs[i] = 2-bit strengths, bits 0-1 / 2-3 = the region's left edge rows 0-3 / 4-7, bits 4-5 / 6-7 = its top edge
- * columns 0-3 / 4-7 (chroma uses the first of each pair, as the reference does).  One slice: the offsets are per picture. */
+ * columns 0-3 / 4-7 (chroma uses the first of each pair, as the reference does).  One slice: the offsets are per picture.
+ * A picture may be filtered in horizontal bands, top to bottom, one call per band: the plane pointers at the band's first row, height =
+ * the band's rows, d_block_data / d_block_bs advanced by (first row / 8) grid rows, width unchanged.  A band must start on a multiple of
+ * 16 luma rows (the chroma horizontal edges are found from the band-local row index), and a call whose first grid row carries top-edge
+ * strengths reads four sample rows (two chroma rows) and one grid row of d_block_data above what it was given and rewrites up to three
+ * (one) of those sample rows: the bands together leave what one call on the whole picture leaves. */
 int havoc_mi355x_deblock(havoc_mi355x_ctx *ctx, int S, int bitDepth, void *d_luma, intptr_t stride_luma, void *d_cb, void *d_cr, intptr_t stride_chroma,
                          int width, int height, const int8_t *d_block_data, const uint8_t *d_block_bs, int tc_offset_div2, int beta_offset_div2,
                          int cb_qp_offset, int cr_qp_offset);
