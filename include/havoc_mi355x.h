@@ -663,6 +663,36 @@ size_t havoc_mi355x_rdoq_workspace(int njobs);
 int havoc_mi355x_rdoq(havoc_mi355x_ctx *ctx, int bitDepth, int log2TrafoSize, int16_t *d_dst, const int16_t *d_src, const uint8_t *d_states,
                       const havoc_mi355x_rdoq_job *d_jobs, int njobs, int32_t *d_cbf, void *d_work, size_t work_bytes);
 
+/* ---- the CABAC rate of residual_coding per transform block (csrc/kernels_residual_rate.hip) ----
+ * The bits the reference's EstimateRate verb measures for one residual_coding (turing/EncodeResidual.hpp:36-301 with H::Tag == EstimateRate<void>, over what
+ * CodedData::storeResidual packs from the n x n raster of levels), bit for bit, as a Cost (Q16, int64).  One job = a chain of `count` blocks of the launch's size, walked in
+ * order from the job's snapshot with the contexts carried from one block to the next: the reference walks the four depth-1 luma blocks of a unit in z-order that way, and
+ * luma residual contexts are moved by luma residuals only, so a chain of four gives the luma residual bits of that tree from the unit's snapshot.
+ *   - a context-coded bin costs the Q15 table entry (turing/Write.h:413-422) shifted to Q16 and MOVES its context (measureEncodeDecision, Write.h:476-492): every bin is
+ *     priced from the state the previous bins of the chain left; a bypass bin costs 1 << 16;
+ *   - sign bits are popcount(sigCoeffFlags) - signHidden whole bits per sub-block; signHidden only with `sdh` and a significant coefficient at scan position >= 3;
+ *   - coeff_abs_level_greater2_flag is priced inside the greater1 loop (the EstimateRate tag), at most 8 greater1 flags per sub-block, the base level of the later
+ *     coefficients from the reference's countdown arithmetic; ctxSet from greater1Ctx / lastGreater1Flag as the previously VISITED sub-block left them (-1 / 1 at the
+ *     start of a block);
+ *   - coded_sub_block_flag only for sub-blocks other than the last and sub-block 0, its context from the right / below neighbours (the `snake` word); the DC sig flag of
+ *     such a sub-block is inferred when no other coefficient of it is significant; sub-block 0 is always visited (empty: its sig flags are priced as zeros);
+ *   - the last position's own sig flag is not priced; scan_idx 2 swaps the x and y of the last position;
+ *   - an all-zero block costs 0 and touches no context (IfCbf).
+ * transform_skip_enabled_flag = 0 and cu_transquant_bypass_flag = 0.  scan_idx != 0 only with log2TrafoSize <= 3, c_idx != 0 only with log2TrafoSize <= 4 (4:2:0).
+ * A job with count outside 1..4, c_idx > 2, scan_idx > 2 or an excluded (size, scan / component) pair is not walked: no level is read, d_rate[rate_index .. rate_index +
+ * min(max(count, 1), 4) - 1] = -1 and its d_states_out is its input snapshot.  level_off, ctx_index and rate_index are trusted, as in havoc_mi355x_rdoq.
+ * d_states is never written.  d_states_out: NULL, or njobs x 128 bytes: the job's snapshot after its last block (bytes outside the residual contexts copied).
+ * d_levels and d_rate 8-byte aligned.  No allocation, no synchronisation, no workspace: capturable into a HIP graph. */
+typedef struct {
+    int32_t level_off;   /* first of `count` blocks of n*n contiguous int16 levels (raster, as havoc_mi355x_rdoq writes them); block k at level_off + k*n*n; multiple of 4 */
+    int32_t ctx_index;   /* the 128-byte snapshot of d_states (HAVOC_RDOQ_CTX_* layout) block 0 starts from */
+    int32_t rate_index;  /* block k's rate -> d_rate[rate_index + k] */
+    uint8_t c_idx, scan_idx, sdh, count;   /* count 1..4: the blocks are walked in order, the contexts carried from one to the next */
+    int32_t reserved[4];
+} havoc_mi355x_residual_rate_job;   /* sizeof: 32 */
+int havoc_mi355x_residual_rate(havoc_mi355x_ctx *ctx, int log2TrafoSize, const int16_t *d_levels, const uint8_t *d_states, const havoc_mi355x_residual_rate_job *d_jobs,
+                               int njobs, int64_t *d_rate, uint8_t *d_states_out);
+
 /* The same two steps with the scan of the coefficients done where they are produced (16x16 / 32x32 blocks; round 3):
  *   tu_forward_scan  = tu_forward + the first pass of the device RDOQ (which 4x4 groups hold a rounded level, the block's energy -> d_work;
  *                      the level block of d_rdoq_jobs[i].dst_off zeroed).  d_rdoq_jobs[i] describes the same block as d_jobs[i]
@@ -711,7 +741,8 @@ int havoc_mi355x_intra_expand(havoc_mi355x_ctx *ctx, const havoc_mi355x_intra_se
                               havoc_mi355x_intra_job *d_intra_jobs, havoc_mi355x_tu_fused_job *d_tu_jobs, havoc_mi355x_rdoq_job *d_rdoq_jobs, int32_t *d_stat_jobs,
                               int32_t *d_owner);
 /* Search.hpp:143-255: the first candidate with the smallest   mode rate + (1 + (cbf ? 2 * nonzero + sum_abs : 0) << 16) + reciprocal_lambda_q16 * ssd.
- * The RATE here is a stand-in, not the reference's: its RD stage charges every mode -- candModeList[0] included -- the bits EstimateRateLuma measures in the CABAC state of
+ * The RATE here is a stand-in, not the reference's (the RESIDUAL term can now be the reference's: havoc_mi355x_residual_rate measures it on the device; the intra chain
+ * does not use it yet, and the mode bits in their CABAC state stay unpriced): its RD stage charges every mode -- candModeList[0] included -- the bits EstimateRateLuma measures in the CABAC state of
  * that moment (prev_intra_luma_pred_flag, mpm_idx / rem_intra_luma_pred_mode, the residual), where this uses the first stage's offsets (rate_a_minus_c is 0 rate for
  * candModeList[0]) and a count of levels.  The order of evaluation, the Q16 arithmetic and the strict comparison are the reference's (pinned with the encoder's own rates:
  * tests/test_trace_pin.py); a caller with an entropy coder supplies real rates through the host form (search/tu_decision.hpp: decideIntraRd with a rate functor);
@@ -724,7 +755,7 @@ int havoc_mi355x_intra_decide(havoc_mi355x_ctx *ctx, const havoc_mi355x_intra_mp
  * reconstructInter's choice between one transform block and four (turing/Reconstruct.cpp:1296-1428; turingcodec_amd/search/tu_decision.hpp: decideRqt) from the outcomes of a
  * unit's five candidate blocks, evaluated by the caller's chain tu_forward -> rdoq -> tu_reconstruct (into pieces) -> level_stats: the split tree first; none of its blocks
  * coded -> the unit stays unsplit without residual and depth 0 is never considered; else the cheaper of  rate + ssd * reciprocal_lambda  wins, depth 0 on `<` (rate = the
- * stand-in of tu_decision.hpp: (1 + (cbf ? 2 * nonzero + sum_abs : 0)) << 16 per block).  Candidate j of size s has its outcome at sizes[s - 2].d_cbf / d_ssd / d_stats [j] and its
+ * stand-in of tu_decision.hpp: (1 + (cbf ? 2 * nonzero + sum_abs : 0)) << 16 per block; havoc_mi355x_rqt_decide_rated below takes the reference's residual bits instead).  Candidate j of size s has its outcome at sizes[s - 2].d_cbf / d_ssd / d_stats [j] and its
  * job at d_jobs[j]; unit i's depth-0 candidate is d_zero_at[i] of its size, its four depth-1 candidates d_one_at[i] .. + 3 of the next smaller size.  d_final[j] = the job that
  * reconstructs candidate j again: into the picture (rec_off = rec_origin + y * rec_stride + x) when it belongs to the chosen tree -- a unit without residual through its four
  * depth-1 blocks -- else at dump_off (any block-sized area of the same allocation nobody reads: the launches after the decision have a fixed size). */
@@ -734,6 +765,13 @@ typedef struct { int32_t depth, tried_zero; havoc_mi355x_tu_outcome zero, one[4]
 typedef struct { const int32_t *d_cbf; const uint32_t *d_ssd; const int32_t *d_stats; const havoc_mi355x_tu_fused_job *d_jobs; havoc_mi355x_tu_fused_job *d_final; } havoc_mi355x_rqt_size;
 int havoc_mi355x_rqt_decide(havoc_mi355x_ctx *ctx, const havoc_mi355x_rqt_unit *d_units, int n, const int32_t *d_zero_at, const int32_t *d_one_at, const havoc_mi355x_rqt_size sizes[4],
                             int64_t rec_origin, intptr_t rec_stride, int32_t dump_off, int32_t reciprocal_lambda_q16, havoc_mi355x_rqt_choice *d_out);
+/* The same decision with the residual term supplied: d_rates[s - 2][j] = the Q16 rate of candidate j of transform size s (havoc_mi355x_residual_rate: the reference's
+ * bits of its residual_coding) in place of the stand-in; a size with tables has its rates.  Order of evaluation, the uncoded short-cut, the Q16 arithmetic, `cost_zero < cost_one`,
+ * the final job records and the 104-byte results are havoc_mi355x_rqt_decide's.  sizes[k].d_stats may be NULL: nonzero / sum_abs of the results are then 0.  With real
+ * residual rates the costs still leave out what the reference charges beside them: cbf_luma, split_transform_flag and the chroma residuals of the tree. */
+int havoc_mi355x_rqt_decide_rated(havoc_mi355x_ctx *ctx, const havoc_mi355x_rqt_unit *d_units, int n, const int32_t *d_zero_at, const int32_t *d_one_at,
+                                  const havoc_mi355x_rqt_size sizes[4], const int64_t *const d_rates[4], int64_t rec_origin, intptr_t rec_stride, int32_t dump_off,
+                                  int32_t reciprocal_lambda_q16, havoc_mi355x_rqt_choice *d_out);
 /* the 4x4 cells havoc_mi355x_derive_bs reads, made from the decisions: every unit one inter 2Nx2N prediction unit from list 0 (decoded picture dpb_index0) at the vector d_field
  * (int16 [2][height / 4][width / 4][2]) holds at its origin, coded flags and transform sizes as decided; cells outside the units: no motion coded, qp, tu_log2 = 2 */
 int havoc_mi355x_block_cells(havoc_mi355x_ctx *ctx, int width, int height, int qp, int dpb_index0, const int16_t *d_field, const havoc_mi355x_rqt_unit *d_units,

@@ -44,7 +44,7 @@ hipError_t launch_intra_decide(hipStream_t, const void *, const int32_t *, const
                                int, int32_t, void *, void *);
 hipError_t launch_merge_jobs(hipStream_t, const void *, const int16_t *, const int32_t *, const int32_t *, int, int, void *, void *, void *, int16_t *);
 hipError_t launch_pred_jobs(hipStream_t, const void *, const int16_t *, int, const int32_t *, const int32_t *, int, int, int, const int32_t *, void *);
-hipError_t launch_rqt_decide(hipStream_t, const void *, int, const int32_t *, const int32_t *, const void *, long, int, int, int32_t, void *);
+hipError_t launch_rqt_decide(hipStream_t, const void *, int, const int32_t *, const int32_t *, const void *, long, int, int, int32_t, void *, const int64_t *const *rates);
 hipError_t launch_block_cells(hipStream_t, int, int, int, int, const int16_t *, const void *, const void *, int, void *, bool);
 hipError_t launch_search_wait_rows(hipStream_t, const void *, int, int, int, int *);
 hipError_t launch_intra_gather(hipStream_t, int, const void *, const void *, const int32_t *, const uint8_t *, const void *, int, const void *, void *, void *);
@@ -60,6 +60,7 @@ hipError_t launch_search_picture_uni(hipStream_t, int S, const havoc_mi355x_sear
                                      const void *, long, const long *, const void *, const int32_t *, int, int, int, void *, void *, int16_t *, void *, int, const int32_t *);
 hipError_t launch_rdoq(hipStream_t, int bd, int log2, int16_t *, const int16_t *, const uint8_t *, const void *, int, int32_t *, void *);
 size_t rdoq_workspace_bytes(int njobs);
+hipError_t launch_residual_rate(hipStream_t, int log2, const int16_t *, const uint8_t *, const void *, int, int64_t *, uint8_t *);
 hipError_t launch_sao_stats(hipStream_t, int S, int bd, const void *, long, const void *, long, const void *, int, int64_t *);
 hipError_t launch_sao_band_chroma(hipStream_t, int S, int bd, const void *, long, const void *, long, const void *, int, int64_t *);
 hipError_t launch_sao_filter(hipStream_t, int S, int bd, void *, long, const void *, long, const void *, int);
@@ -96,6 +97,7 @@ static_assert(offsetof(havoc_mi355x_sao_params, dist_sao) == 88 && offsetof(havo
               "sao record ABI");
 static_assert(sizeof(havoc_mi355x_sao_decision) == 128 && offsetof(havoc_mi355x_sao_decision, merge_left) == 88 &&
               offsetof(havoc_mi355x_sao_decision, ctx_merge_before) == 104 && offsetof(havoc_mi355x_sao_decision, decided) == 108, "sao record ABI");
+static_assert(sizeof(havoc_mi355x_residual_rate_job) == 32 && offsetof(havoc_mi355x_residual_rate_job, c_idx) == 12, "job ABI");
 static_assert(sizeof(havoc_mi355x_intra_mpm) == 40 && sizeof(havoc_mi355x_intra_choice) == 40, "job ABI");
 
 #include "ctx.h"
@@ -771,7 +773,27 @@ int havoc_mi355x_rqt_decide(havoc_mi355x_ctx *ctx, const havoc_mi355x_rqt_unit *
             const bool all = z.d_cbf && z.d_ssd && z.d_stats && z.d_jobs && z.d_final, none = !z.d_cbf && !z.d_ssd && !z.d_stats && !z.d_jobs && !z.d_final;
             REQUIRE(all || none, "rqt_decide: a size table with some null pointers");
         }
-    return check(launch_rqt_decide(LS(ctx), d_units, n, d_zero_at, d_one_at, sizes, (long)rec_origin, (int)rec_stride, dump_off, reciprocal_lambda_q16, d_out), "rqt_decide");
+    return check(launch_rqt_decide(LS(ctx), d_units, n, d_zero_at, d_one_at, sizes, (long)rec_origin, (int)rec_stride, dump_off, reciprocal_lambda_q16, d_out, nullptr), "rqt_decide");
+}
+
+int havoc_mi355x_rqt_decide_rated(havoc_mi355x_ctx *ctx, const havoc_mi355x_rqt_unit *d_units, int n, const int32_t *d_zero_at, const int32_t *d_one_at,
+                                  const havoc_mi355x_rqt_size sizes[4], const int64_t *const d_rates[4], int64_t rec_origin, intptr_t rec_stride, int32_t dump_off,
+                                  int32_t reciprocal_lambda_q16, havoc_mi355x_rqt_choice *d_out)
+{
+    REQUIRE_CTX(); REQUIRE(n >= 0, "n < 0"); REQUIRE(sizes != nullptr, "null sizes"); REQUIRE(d_rates != nullptr, "rqt_decide_rated: null d_rates");
+    REQUIRE(rec_stride > 0 && rec_stride < (1 << 24), "rec_stride out of range");
+    REQUIRE(n == 0 || (d_units && d_zero_at && d_one_at && d_out), "null device pointer");
+    REQUIRE(reciprocal_lambda_q16 >= 0, "reciprocal_lambda_q16 < 0"); REQUIRE(dump_off >= 0, "dump_off < 0");
+    if (n > 0)      // as havoc_mi355x_rqt_decide; d_stats may be null (nonzero / sum_abs are then 0), a size with tables has its rates
+        for (int k = 0; k < 4; ++k)
+        {
+            const havoc_mi355x_rqt_size &z = sizes[k];
+            const bool all = z.d_cbf && z.d_ssd && z.d_jobs && z.d_final, none = !z.d_cbf && !z.d_ssd && !z.d_stats && !z.d_jobs && !z.d_final;
+            REQUIRE(all || none, "rqt_decide_rated: a size table with some null pointers");
+            REQUIRE(none || d_rates[k], "rqt_decide_rated: a size table without its rates");
+        }
+    return check(launch_rqt_decide(LS(ctx), d_units, n, d_zero_at, d_one_at, sizes, (long)rec_origin, (int)rec_stride, dump_off, reciprocal_lambda_q16, d_out, d_rates),
+                 "rqt_decide_rated");
 }
 
 int havoc_mi355x_block_cells(havoc_mi355x_ctx *ctx, int width, int height, int qp, int dpb_index0, const int16_t *d_field, const havoc_mi355x_rqt_unit *d_units,
@@ -1044,6 +1066,16 @@ int havoc_mi355x_rdoq(havoc_mi355x_ctx *ctx, int bitDepth, int log2TrafoSize, in
     REQUIRE(njobs == 0 || log2TrafoSize <= 3 || (d_work && work_bytes >= rdoq_workspace_bytes(njobs) && (reinterpret_cast<uintptr_t>(d_work) & 15) == 0),
             "rdoq: workspace missing, misaligned or smaller than havoc_mi355x_rdoq_workspace(njobs)");
     return check(launch_rdoq(LS(ctx), bitDepth, log2TrafoSize, d_dst, d_src, d_states, d_jobs, njobs, d_cbf, d_work), "rdoq");
+}
+
+int havoc_mi355x_residual_rate(havoc_mi355x_ctx *ctx, int log2TrafoSize, const int16_t *d_levels, const uint8_t *d_states, const havoc_mi355x_residual_rate_job *d_jobs,
+                               int njobs, int64_t *d_rate, uint8_t *d_states_out)
+{
+    REQUIRE_CTX(); REQUIRE(log2TrafoSize >= 2 && log2TrafoSize <= 5, "log2TrafoSize must be 2..5"); REQUIRE(njobs >= 0, "njobs < 0");
+    REQUIRE(d_levels && d_states && d_jobs && d_rate, "residual_rate: null device pointer");
+    REQUIRE((reinterpret_cast<uintptr_t>(d_levels) & 7) == 0 && (reinterpret_cast<uintptr_t>(d_rate) & 7) == 0, "residual_rate: d_levels and d_rate must be 8-byte aligned");
+    REQUIRE(d_states_out != d_states, "residual_rate: d_states_out must not be d_states (which is never written)");
+    return check(launch_residual_rate(LS(ctx), log2TrafoSize, d_levels, d_states, d_jobs, njobs, d_rate, d_states_out), "residual_rate");
 }
 
 } // extern "C"

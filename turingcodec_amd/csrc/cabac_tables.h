@@ -1,6 +1,7 @@
 // CABAC tables shared by the kernels that estimate rates: the bits of a bin from each context state, and the spec's state transitions.
 #pragma once
 
+#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace havoc_gpu {
@@ -23,6 +24,30 @@ __device__ const int32_t kEntropyBits[128] = {
 __device__ const uint8_t kTransIdxLps[64] = {
     0, 0, 1, 2, 2, 4, 4, 5, 6, 7, 8, 9, 9, 11, 11, 12, 13, 13, 15, 15, 16, 16, 18, 18, 19, 19, 21, 21, 22, 22, 23, 24,
     24, 25, 26, 26, 27, 27, 28, 29, 29, 30, 30, 30, 31, 32, 32, 33, 33, 33, 34, 34, 35, 35, 35, 36, 36, 36, 37, 37, 37, 38, 38, 63 };
+
+// measureEncodeDecision (Write.h:476-492) as the context-updating EstimateRate uses it (Search<sao>::go, residual_coding): the Q15 bits of the bin from this
+// state, as a Q16 Cost, then the state transition of H.265 9.3.4.3.2.2 (kTransIdxLps; an LPS in state 0 swaps the MPS).  Entry
+// 2 state + bin of a walk's LDS table: the new state | the rate << 8 (a walk prices its dependent bins with one LDS read each)
+__device__ __forceinline__ int bin_entry(int state, int bin)
+{
+    const int i = state ^ bin, p = state >> 1;
+    int mps = state & 1, np;
+    if (i & 1)
+    {
+        np = kTransIdxLps[p];
+        if (p == 0) mps = bin;
+    }
+    else
+        np = p < 62 ? p + 1 : p;
+    return (np << 1 | mps) | kEntropyBits[i] << 9;
+}
+
+__device__ __forceinline__ long long ctx_bin(const int *table, int &state, int bin)
+{
+    const int e = table[2 * state + bin];
+    state = e & 0xff;
+    return (long long)(e >> 8);
+}
 
 } // namespace
 

@@ -128,7 +128,7 @@ __global__ __launch_bounds__(256) void k_intra_decide(const IntraCtx *__restrict
     {
         const int mode = order[kMaxOrder * (long)i + j], s = base + j;
         const int64_t modeRate = mode == c.cand[0] ? c.rateA : ((mode == c.cand[1] || mode == c.cand[2]) ? c.rateB : 0);
-        const int64_t tuRate = (int64_t)(1 + (cbf[s] ? 2 * stats[2 * s] + stats[2 * s + 1] : 0)) << 16;      // search/tu_decision.hpp: tuRate (stand-in)
+        const int64_t tuRate = (int64_t)(1 + (cbf[s] ? 2 * stats[2 * s] + stats[2 * s + 1] : 0)) << 16;      // search/tu_decision.hpp: tuRate (stand-in; havoc_mi355x_residual_rate has the reference's residual bits, not used here yet)
         const int64_t cost = modeRate + tuRate + (int64_t)reciprocalLambdaQ16 * (int64_t)(int32_t)ssd[s];
         ++r.evaluated;
         if (cost < r.cost)
@@ -153,7 +153,8 @@ __global__ __launch_bounds__(256) void k_intra_decide(const IntraCtx *__restrict
 // ---- the transform-tree decision of inter units and the picture's block structure, ON THE DEVICE (round 4) -----------------------------------------------
 // search/tu_decision.hpp's decideRqt (turing/Reconstruct.cpp:1296-1428) restated lane per unit over the outcomes of its five candidate blocks (depth 0: one block,
 // depth 1: four, evaluated by the chain tu_forward -> rdoq -> tu_reconstruct -> level_stats), so that a picture's launches after its searches need no host in
-// between: the decision, the job records that reconstruct EVERY candidate -- the chosen ones into the picture, the others into a dump area (a fixed number of jobs per
+// between (the residual term is the stand-in of tu_decision.hpp, or -- RATED -- the reference's bits of each candidate's residual_coding from
+// kernels_residual_rate.hip; cbf_luma, split_transform_flag and the chroma residuals are priced by neither): the decision, the job records that reconstruct EVERY candidate -- the chosen ones into the picture, the others into a dump area (a fixed number of jobs per
 // size: the sequence can be recorded into a HIP graph) -- and the 4x4 cells havoc_mi355x_derive_bs reads.  The host forms stay: tests hold these against them.
 struct RqtUnit { int32_t x0, y0, log2, ctxIndex; };                                                                          // havoc_rqt_cu
 struct TuOutcome { int32_t cbf; uint32_t ssd; int32_t nonzero, sumAbs; };                                                    // havoc_tu_outcome
@@ -163,11 +164,19 @@ struct RqtSizes { RqtSize s[4]; };
 struct Cell { int16_t mv[2][2]; int8_t dpb[2]; uint8_t flags; int8_t qpY; uint8_t tuLog2; uint8_t reserved[3]; };            // havoc_mi355x_cell
 static_assert(sizeof(RqtUnit) == 16 && sizeof(TuOutcome) == 16 && sizeof(RqtResult) == 104 && sizeof(RqtSize) == 40 && sizeof(Cell) == 16, "record layouts");
 
-__device__ __forceinline__ TuOutcome outcomeOf(const RqtSize &z, int j) { return TuOutcome{z.cbf[j], z.ssd[j], z.stats[2 * j], z.stats[2 * j + 1]}; }
+struct RqtRates { const int64_t *r[4]; };      // havoc_mi355x_rqt_decide_rated: the Q16 rate of candidate j of each transform size
+
+__device__ __forceinline__ TuOutcome outcomeOf(const RqtSize &z, int j)
+{
+    return z.stats ? TuOutcome{z.cbf[j], z.ssd[j], z.stats[2 * j], z.stats[2 * j + 1]} : TuOutcome{z.cbf[j], z.ssd[j], 0, 0};      // (no level statistics: the rated form)
+}
 __device__ __forceinline__ int64_t tuRateOf(const TuOutcome &t) { return (int64_t)(1 + (t.cbf ? 2 * t.nonzero + t.sumAbs : 0)) << 16; }      // tu_decision.hpp: tuRate (stand-in)
 
+// RATED: the residual term is the caller's rate of each candidate (havoc_mi355x_residual_rate: the reference's bits) in place of the stand-in; nothing else differs
+template <bool RATED>
 __global__ __launch_bounds__(256) void k_rqt_decide(const RqtUnit *__restrict__ units, int n, const int32_t *__restrict__ zeroAt, const int32_t *__restrict__ oneAt,
-                                                    const RqtSizes z, long recOrigin, int recStride, int dumpOff, int32_t reciprocalLambdaQ16, RqtResult *__restrict__ out)
+                                                    const RqtSizes z, const RqtRates rates, long recOrigin, int recStride, int dumpOff, int32_t reciprocalLambdaQ16,
+                                                    RqtResult *__restrict__ out)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -190,14 +199,14 @@ __global__ __launch_bounds__(256) void k_rqt_decide(const RqtUnit *__restrict__ 
         r.one[k] = outcomeOf(s1, j1 + k);
         ssdOne += (int32_t)r.one[k].ssd;
         coded |= r.one[k].cbf != 0;
-        rateOne += tuRateOf(r.one[k]);
+        rateOne += RATED ? rates.r[u.log2 - 3][j1 + k] : tuRateOf(r.one[k]);
     }
     r.costOne = rateOne + (int64_t)reciprocalLambdaQ16 * (int64_t)ssdOne;
     if (coded)
     {
         r.triedZero = 1;
         r.zero = outcomeOf(s0, j0);
-        r.costZero = tuRateOf(r.zero) + (int64_t)reciprocalLambdaQ16 * (int64_t)(int32_t)r.zero.ssd;
+        r.costZero = (RATED ? rates.r[u.log2 - 2][j0] : tuRateOf(r.zero)) + (int64_t)reciprocalLambdaQ16 * (int64_t)(int32_t)r.zero.ssd;
         r.depth = r.costZero < r.costOne ? 0 : 1;      // Reconstruct.cpp:1389
     }
     out[i] = r;
@@ -255,11 +264,15 @@ __global__ __launch_bounds__(64) void k_block_cells(const RqtUnit *__restrict__ 
 }
 
 hipError_t launch_rqt_decide(hipStream_t st, const void *units, int n, const int32_t *zeroAt, const int32_t *oneAt, const void *sizes, long recOrigin, int recStride, int dumpOff,
-                             int32_t rlQ16, void *out)
+                             int32_t rlQ16, void *out, const int64_t *const *rates)
 {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_rqt_decide, dim3((n + 255) / 256), dim3(256), 0, st, (const RqtUnit *)units, n, zeroAt, oneAt, *static_cast<const RqtSizes *>(sizes), recOrigin, recStride,
-                       dumpOff, rlQ16, (RqtResult *)out);
+    if (rates)
+        hipLaunchKernelGGL(k_rqt_decide<true>, dim3((n + 255) / 256), dim3(256), 0, st, (const RqtUnit *)units, n, zeroAt, oneAt, *static_cast<const RqtSizes *>(sizes),
+                           RqtRates{{rates[0], rates[1], rates[2], rates[3]}}, recOrigin, recStride, dumpOff, rlQ16, (RqtResult *)out);
+    else
+        hipLaunchKernelGGL(k_rqt_decide<false>, dim3((n + 255) / 256), dim3(256), 0, st, (const RqtUnit *)units, n, zeroAt, oneAt, *static_cast<const RqtSizes *>(sizes),
+                           RqtRates(), recOrigin, recStride, dumpOff, rlQ16, (RqtResult *)out);
     return hipGetLastError();
 }
 

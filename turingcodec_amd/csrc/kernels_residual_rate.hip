@@ -1,0 +1,277 @@
+// k_residual_rate: the bits the reference's EstimateRate verb measures for one residual_coding, per transform block.
+//
+// Reference: EncodeResidual::inner<havePopcnt, is4x4, H> with H::Tag == EstimateRate<void> (turing/EncodeResidual.hpp:36-301) over the coded data
+// CodedData::storeResidual (turing/CodedData.h:457-517) packs from an n x n raster of levels; WriteLastSigPrefix / WriteLastSigSuffix
+// (turing/Binarization.h:854-931), CtxIncSigCoeffFlagCalculator (turing/Write.h:1292-1392), the remaining-level estimate
+// (turing/Binarization.h:1199-1238) and measureEncodeDecision (turing/Write.h:476-492).  The rate is a Cost (Q16, int64): a context-coded bin costs the Q15
+// table entry shifted to Q16 and MOVES its context, a bypass bin costs 1 << 16; every bin is priced from the state the previous bins left.
+//
+// Form: a lane per job, sequential (the step is bound by vector-instruction issue and a lane-per-block walk beat a wavefront-parallel one for the
+// quantiser that produces these levels).  A job is a chain of 1..4 blocks walked in order with the contexts running on -- the four depth-1 luma blocks of a unit --
+// so the 128 context states of a job live in a column of the workgroup's LDS copy from its first bin to its last, beside the (state, bin) -> (state, rate)
+// table of cabac_tables.h.  Per 4x4 sub-block, from the highest in scan order down: sixteen levels are loaded (four 8-byte rows) and kept in LDS by raster
+// position; ONE pass over the scan positions 15..0 prices sig_coeff_flag, coeff_abs_level_greater1_flag (at most eight), the one coeff_abs_level_greater2_flag
+// (inside the greater1 loop, as the EstimateRate tag does) and the bypass bins of coeff_abs_level_remaining: the three context families are disjoint and only
+// the order WITHIN a context matters.  Sign bits are popcount(sig) - signHidden.  The `snake` word of coded-sub-block flags, greater1Ctx / lastGreater1Flag
+// carried from the previously visited sub-block, countdown1 / countdown2 as a count of flags and "a greater1 was seen" are the reference's, restated.
+#include "common.h"
+#include "cabac_tables.h"
+
+namespace havoc_gpu {
+
+namespace {
+
+struct RateJob { int32_t level_off, ctx_index, rate_index; uint8_t c_idx, scan_idx, sdh, count; int32_t reserved[4]; };
+static_assert(sizeof(RateJob) == 32 && sizeof(RateJob) == sizeof(havoc_mi355x_residual_rate_job), "residual rate job layout");
+
+enum { kLastX = HAVOC_RDOQ_CTX_LAST_X, kLastY = HAVOC_RDOQ_CTX_LAST_Y, kCsbf = HAVOC_RDOQ_CTX_CSBF, kSig = HAVOC_RDOQ_CTX_SIG, kG1 = HAVOC_RDOQ_CTX_GREATER1,
+       kG2 = HAVOC_RDOQ_CTX_GREATER2 };
+
+// the 4x4 scan as 16 nibbles x | y << 2 (ScanOrder.h:31-97 for a 4x4 block)
+__host__ __device__ constexpr uint64_t scanNibbles(int scanIdx)
+{
+    uint64_t v = 0;
+    int i = 0;
+    if (scanIdx == 0)
+    {
+        for (int d = 0; d < 7; ++d)
+            for (int x = 0; x <= d; ++x)
+                if (x < 4 && d - x < 4) { v |= (uint64_t)(x | (d - x) << 2) << (4 * i); ++i; }
+    }
+    else
+        for (; i < 16; ++i) v |= (uint64_t)(scanIdx == 1 ? i : (i >> 2) | (i & 3) << 2) << (4 * i);
+    return v;
+}
+
+// Write.h:1331-1355 ctxIdxMap[codedSubBlockFlags][raster position in the sub-block]
+__device__ __forceinline__ int sigPattern(int neighbours, int xp, int yp)
+{
+    if (neighbours == 0) return xp + yp == 0 ? 2 : (xp + yp < 3 ? 1 : 0);
+    if (neighbours == 1) return yp == 0 ? 2 : (yp == 1 ? 1 : 0);
+    if (neighbours == 2) return xp == 0 ? 2 : (xp == 1 ? 1 : 0);
+    return 2;
+}
+
+// Write.h:1284: groupIdx, the prefix of a last-significant coordinate
+__device__ __forceinline__ int lastGroup(int c) { return c < 4 ? c : (c < 8 ? 4 + ((c - 4) >> 1) : (c < 16 ? 6 + ((c - 8) >> 2) : 8 + ((c - 16) >> 3))); }
+
+struct RateLds
+{
+    int bins[256];              // 2 state + bin -> new state | Q16 rate << 8
+    uint8_t st[128][64];        // the jobs' context states, [context][lane]
+    int16_t lev[16][64];        // the current sub-block's levels, [raster position][lane]
+    uint32_t cls[3][4];         // per scan and neighbour case: the scan positions whose sigPattern is 1 | those where it is 2, << 16
+    uint8_t subXy[64];          // the diagonal scan of the block's sub-blocks: x | y << 4
+    int32_t ctxIndex[64];
+};
+
+template <int LOG2>
+__global__ __launch_bounds__(64) void k_residual_rate(const int16_t *__restrict__ levels, const uint8_t *__restrict__ states, const RateJob *__restrict__ jobs, int njobs,
+                                                      int64_t *__restrict__ rates, uint8_t *__restrict__ statesOut)
+{
+    constexpr int N = 1 << LOG2, GW = N / 4, NSUB = GW * GW;
+    __shared__ RateLds sh;
+    const int lane = threadIdx.x, first = blockIdx.x * 64, j = first + lane;
+    for (int k = lane; k < 256; k += 64) sh.bins[k] = bin_entry(k >> 1, k & 1);
+    if (lane < 12)
+    {
+        const int t = lane >> 2, nb = lane & 3;
+        const uint64_t sc = t == 0 ? scanNibbles(0) : (t == 1 ? scanNibbles(1) : scanNibbles(2));
+        uint32_t one = 0, two = 0;
+        for (int n = 0; n < 16; ++n)
+        {
+            const int nib = (int)(sc >> (4 * n)) & 15, p = sigPattern(nb, nib & 3, nib >> 2);
+            one |= (uint32_t)(p == 1) << n;
+            two |= (uint32_t)(p == 2) << n;
+        }
+        sh.cls[t][nb] = one | two << 16;
+    }
+    if (lane < NSUB)
+    {   // ScanOrder.h:31-59 applied to the GW x GW sub-blocks
+        int pos = lane, x = 0, y = 0;
+        for (int d = 0; d < 2 * GW - 1; ++d)
+        {
+            const int lo = d < GW ? 0 : d - GW + 1, hi = d < GW ? d : GW - 1, len = hi - lo + 1;
+            if (pos < len) { x = lo + pos; y = d - x; break; }
+            pos -= len;
+        }
+        sh.subXy[lane] = (uint8_t)(x | y << 4);
+    }
+    RateJob job = RateJob();
+    if (j < njobs) job = jobs[j];
+    // a job the entry point excludes is not walked: its rates become -1 and its snapshot passes through
+    const bool valid = j < njobs && job.count >= 1 && job.count <= 4 && job.c_idx <= 2 && job.scan_idx <= 2 && (job.scan_idx == 0 || LOG2 <= 3) && (job.c_idx == 0 || LOG2 <= 4);
+    sh.ctxIndex[lane] = j < njobs ? job.ctx_index : -1;
+    __syncthreads();
+    for (int k = 0; k < 128; ++k)
+    {   // 64 consecutive bytes of a snapshot per step
+        const int idx = k * 64 + lane, jj = idx >> 7, byte = idx & 127, ci = sh.ctxIndex[jj];
+        if (ci >= 0) sh.st[byte][jj] = states[(long)ci * 128 + byte];
+    }
+    __syncthreads();
+    auto price = [&](int ctx, int bin) -> int {
+        const int e = sh.bins[2 * sh.st[ctx][lane] + bin];
+        sh.st[ctx][lane] = (uint8_t)e;
+        return e >> 8;
+    };
+    const int cIdx = job.c_idx, scanIdx = job.scan_idx;
+    const uint64_t scan4 = scanIdx == 0 ? scanNibbles(0) : (scanIdx == 1 ? scanNibbles(1) : scanNibbles(2));
+    const int blocks = valid ? job.count : 0;
+    for (int blk = 0; blk < blocks; ++blk)
+    {
+        const int16_t *src = levels + (long)job.level_off + (long)blk * (N * N);
+        int64_t rate = 0;
+        bool seen = false;                       // the last significant sub-block has been met
+        int lastG1 = 1, c1 = -1;                 // lastGreater1Flag, greater1Ctx (EncodeResidual.hpp:83-84)
+        uint32_t snake = 0;
+        for (int i = NSUB - 1; i >= 0; --i)
+        {
+            int xS = 0, yS = 0;
+            if (GW > 1)
+            {
+                if (scanIdx == 1) { xS = i & (GW - 1); yS = i / GW; }
+                else if (scanIdx == 2) { xS = i / GW; yS = i & (GW - 1); }
+                else { const int p = sh.subXy[i]; xS = p & 15; yS = p >> 4; }
+            }
+            const int16_t *sb = src + (yS * 4) * N + xS * 4;
+            uint32_t any = 0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+            {
+                const uint2 w = *reinterpret_cast<const uint2 *>(sb + r * N);
+                any |= w.x | w.y;
+                sh.lev[4 * r + 0][lane] = (int16_t)(w.x & 0xffff);
+                sh.lev[4 * r + 1][lane] = (int16_t)(w.x >> 16);
+                sh.lev[4 * r + 2][lane] = (int16_t)(w.y & 0xffff);
+                sh.lev[4 * r + 3][lane] = (int16_t)(w.y >> 16);
+            }
+            const bool coded = any != 0;
+            if (!seen && !coded) continue;       // above the last significant sub-block: nothing is coded
+            const bool isLast = !seen;
+            // sig: bit n = scan position n is significant; mag: CodedData's values (`value = -value` in int16: -32768 stays negative, so it is no greater1)
+            uint32_t sig = 0;
+            if (coded)
+#pragma unroll
+                for (int n = 0; n < 16; ++n) sig |= (uint32_t)(sh.lev[(int)(scan4 >> (4 * n)) & 15][lane] != 0) << n;
+            int ctxBits = 0, bypass = 0;
+            int lastPos = 16;                    // sig flags are priced below this scan position
+            if (isLast)
+            {
+                seen = true;
+                lastPos = 31 - __clz(sig);
+                const int nib = (int)(scan4 >> (4 * lastPos)) & 15, xC = (xS << 2) + (nib & 3), yC = (yS << 2) + (nib >> 2);
+                // last_sig_coeff_{x,y}_prefix: truncated unary, cMax = 2 log2 - 1 (Binarization.h:854-899); the suffix is bypass; scanIdx 2 swaps x and y
+                const int ctxOffset = cIdx ? 15 : 3 * (LOG2 - 2) + ((LOG2 - 1) >> 2), ctxShift = cIdx ? LOG2 - 2 : (LOG2 + 1) >> 2, cMax = 2 * LOG2 - 1;
+                for (int c = 0; c < 2; ++c)
+                {
+                    const int v = (c == 0) == (scanIdx != 2) ? xC : yC, prefix = lastGroup(v), base = c == 0 ? kLastX : kLastY;
+                    for (int b = 0; b < prefix; ++b) ctxBits += price(base + ctxOffset + (b >> ctxShift), 1);
+                    if (prefix < cMax) ctxBits += price(base + ctxOffset + (prefix >> ctxShift), 0);
+                    if (prefix > 3) bypass += (prefix >> 1) - 1;
+                }
+            }
+            const int d = 7 + yS - xS, neighbours = (int)(snake >> d) & 3;      // EncodeResidual.hpp:98-102
+            snake &= ~(3u << d);
+            if (coded) snake |= 3u << d;
+            bool infer = false;
+            if (!isLast && i != 0)
+            {
+                ctxBits += price(kCsbf + (cIdx ? 2 : 0) + (neighbours ? 1 : 0), coded);
+                infer = true;
+            }
+            if (coded || i == 0)
+            {
+                if (sig & 0xfffe) infer = false;
+                // sig_coeff_flag's context (Write.h:1292-1392)
+                const uint32_t cls = sh.cls[scanIdx][neighbours];
+                int sigBase;
+                if (LOG2 == 2) sigBase = 0;
+                else if (cIdx == 0) sigBase = (i != 0 ? 3 : 0) + (LOG2 == 3 ? (scanIdx == 0 ? 9 : 15) : 21);
+                else sigBase = LOG2 == 3 ? 9 : 12;
+                const int ctxSet = ((i != 0 && cIdx == 0) ? 2 : 0) | (((c1 > 0 && lastG1) || c1 == 0) ? 1 : 0);
+                c1 = 1;
+                const int g1Base = kG1 + ctxSet * 4 + (cIdx ? 16 : 0);
+                int numG1 = 0, rice = 0;
+                bool g2Done = false, sawG1 = false;
+                for (int n = 15; n >= 0; --n)
+                {
+                    const int s = (int)(sig >> n) & 1;
+                    if (n < lastPos && !(n == 0 && infer))
+                    {
+                        int inc;
+                        if (LOG2 == 2) inc = (int)(0x8877886654325410ull >> (4 * ((int)(scan4 >> (4 * n)) & 15))) & 15;      // 0 1 4 5 / 2 3 4 5 / 6 6 8 8 / 7 7 8 8
+                        else if (i == 0 && n == 0) inc = 0;
+                        else inc = sigBase + ((int)(cls >> n) & 1) + 2 * ((int)(cls >> (16 + n)) & 1);
+                        ctxBits += price(kSig + (cIdx ? 27 : 0) + inc, s);
+                    }
+                    if (!s) continue;
+                    const int v = sh.lev[(int)(scan4 >> (4 * n)) & 15][lane];
+                    const int mag = v < 0 ? (int)(int16_t)(-v) : v;
+                    const int g1 = mag > 1;
+                    // the base level: 3 while the first eight flags run and no greater1 was seen, then 2; 1 from the ninth (countdown1 / countdown2, :265-283)
+                    const int base = numG1 < 8 ? (sawG1 ? 2 : 3) : 1;
+                    if (numG1 < 8)
+                    {
+                        ctxBits += price(g1Base + c1, g1);
+                        if (c1 > 0) lastG1 = g1;
+                        if (g1 && !g2Done)
+                        {
+                            g2Done = true;
+                            ctxBits += price(kG2 + ctxSet + (cIdx ? 4 : 0), mag > 2);
+                        }
+                        if (++numG1 < 8)      // (the reference breaks out of the loop at the eighth flag before it moves greater1Ctx)
+                        {
+                            if (lastG1) c1 = 0;
+                            else if (c1 < 3) ++c1;
+                        }
+                    }
+                    else
+                        ++numG1;
+                    sawG1 |= g1 != 0;
+                    const int absCoeff = g1 ? (mag & 0xffff) : 1, remaining = absCoeff - base;
+                    if (remaining >= 0)
+                    {   // Binarization.h:1205-1237
+                        const int a = (remaining >> rice) - 3;
+                        bypass += rice + 4 + (a < 0 ? a : 2 * (31 - __clz(a + 1)));
+                        rice = min(rice + (absCoeff > (3 << rice) ? 1 : 0), 4);
+                    }
+                }
+                // coeff_sign_flag: whole bits, one less when the sign of the first coefficient is hidden (:190-249)
+                int signBits = __popc(sig);
+                if (job.sdh && (sig & 0xfff8) && (31 - __clz(sig)) - (__ffs(sig) - 1) > 3) --signBits;
+                bypass += signBits;
+            }
+            rate += (int64_t)ctxBits + ((int64_t)bypass << 16);
+        }
+        rates[(long)job.rate_index + blk] = rate;      // (an all-zero block: IfCbf skips it, rate 0, no context touched)
+    }
+    if (j < njobs && !valid)
+    {
+        const int c = job.count < 1 ? 1 : (job.count > 4 ? 4 : job.count);
+        for (int blk = 0; blk < c; ++blk) rates[(long)job.rate_index + blk] = -1;
+    }
+    if (statesOut == nullptr) return;
+    __syncthreads();
+    for (int k = 0; k < 128; ++k)
+    {
+        const int idx = k * 64 + lane, jj = idx >> 7, byte = idx & 127;
+        if (first + jj < njobs) statesOut[(long)(first + jj) * 128 + byte] = sh.st[byte][jj];
+    }
+}
+
+} // namespace
+
+hipError_t launch_residual_rate(hipStream_t st, int log2, const int16_t *levels, const uint8_t *states, const void *jobs, int njobs, int64_t *rates, uint8_t *statesOut)
+{
+    if (njobs <= 0) return hipSuccess;
+    const RateJob *j = static_cast<const RateJob *>(jobs);
+    const dim3 grid((njobs + 63) / 64), wg(64);
+    if (log2 == 2) hipLaunchKernelGGL(k_residual_rate<2>, grid, wg, 0, st, levels, states, j, njobs, rates, statesOut);
+    else if (log2 == 3) hipLaunchKernelGGL(k_residual_rate<3>, grid, wg, 0, st, levels, states, j, njobs, rates, statesOut);
+    else if (log2 == 4) hipLaunchKernelGGL(k_residual_rate<4>, grid, wg, 0, st, levels, states, j, njobs, rates, statesOut);
+    else if (log2 == 5) hipLaunchKernelGGL(k_residual_rate<5>, grid, wg, 0, st, levels, states, j, njobs, rates, statesOut);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+} // namespace havoc_gpu

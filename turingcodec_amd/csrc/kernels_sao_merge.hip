@@ -93,30 +93,6 @@ __device__ int ctu_dist(const SaoCtu &c, const SaoComp *gcomp, FilterLds &F, con
     return (int32_t)(s[0] + s[1] * 4u + s[2] * 4u);
 }
 
-// measureEncodeDecision (Write.h:476-492) as Search<sao>::go's context-updating EstimateRate uses it: the Q15 bits of the bin from this
-// state, as a Q16 Cost, then the state transition of H.265 9.3.4.3.2.2 (kTransIdxLps; an LPS in state 0 swaps the MPS).  Entry
-// 2 state + bin of the walk's LDS table: the new state | the rate << 8 (the walk prices up to ten dependent bins per CTU: one LDS read each)
-__device__ __forceinline__ int bin_entry(int state, int bin)
-{
-    const int i = state ^ bin, p = state >> 1;
-    int mps = state & 1, np;
-    if (i & 1)
-    {
-        np = kTransIdxLps[p];
-        if (p == 0) mps = bin;
-    }
-    else
-        np = p < 62 ? p + 1 : p;
-    return (np << 1 | mps) | kEntropyBits[i] << 9;
-}
-
-__device__ __forceinline__ long long ctx_bin(const int *table, int &state, int bin)
-{
-    const int e = table[2 * state + bin];
-    state = e & 0xff;
-    return (long long)(e >> 8);
-}
-
 template <int S>
 __global__ __launch_bounds__(256) void k_sao_merge_pre(const SaoCtu *__restrict__ ctus, const SaoParams *__restrict__ params, int cx, MergeWork wk,
                                                        int bd, Planes P)

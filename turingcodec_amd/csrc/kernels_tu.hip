@@ -148,8 +148,8 @@ __global__ __launch_bounds__(256) void k_quantize(int16_t *__restrict__ dst, con
 }
 
 // What a rate estimate reads of a block of quantised levels without downloading them: out[2 * job] = number of non-zero levels,
-// out[2 * job + 1] = sum of |level| (the encoder's EstimateRate<residual_coding> walks the levels themselves on the host; a batch client
-// that decides between transform-tree candidates wants these per candidate).  jobs: (offset, n) pairs, n a multiple of 2.
+// out[2 * job + 1] = sum of |level| (the inputs of the stand-in rate of search/tu_decision.hpp; the encoder's EstimateRate<residual_coding> walks the levels
+// themselves, which kernels_residual_rate.hip does on the device: a transform-tree decision that prices with those bits does not need this kernel).  jobs: (offset, n) pairs, n a multiple of 2.
 __global__ __launch_bounds__(256) void k_level_stats(const int16_t *__restrict__ levels, const int32_t *__restrict__ jobs, int njobs, int32_t *__restrict__ out)
 {
     const int job = xcd_block(blockIdx.x, gridDim.x) * 4 + (threadIdx.x >> 6);

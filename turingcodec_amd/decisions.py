@@ -421,10 +421,14 @@ class DecisionPicture:
     PAD = 96
 
     def __init__(self, hv, width, height, bit_depth=8, qp=32, seed=11, threads=16, frames=None, density=1.0, intra=True, search_on_device=True, distance=1,
-                 sao=False):
+                 sao=False, residual_rates=False):
         import torch
         if sao and not search_on_device:
             raise ValueError("sao=True needs the device route (search_on_device=True)")
+        if residual_rates and not search_on_device:
+            raise ValueError("residual_rates=True needs the device route (search_on_device=True)")
+        # the transform-tree decision prices each candidate's residual with the reference's CABAC bits (havoc_mi355x_residual_rate) in place of the stand-in
+        self.residual_rates = residual_rates
         self.sao = sao                                # in-loop SAO between deblocking and padding (sao_filter_inputs / sao_loop_filter)
         from . import havoc as hmod
         from . import workload
@@ -701,7 +705,7 @@ class DecisionPicture:
             one_at[i] = len(lists[L - 1])
             lists[L - 1] += [(i, 1, k) for k in range(4)]
         plan = dict(sizes={}, d_units=hv.up(np.ascontiguousarray(u).view(np.int32)), d_zero_at=hv.up(zero_at), d_one_at=hv.up(one_at),
-                    d_out=hv.zeros(len(u) * 26, np.int32), table=np.zeros((4, 5), np.uint64), launches=0)
+                    d_out=hv.zeros(len(u) * 26, np.int32), table=np.zeros((4, 5), np.uint64), rates=np.zeros(4, np.uint64), launches=0)
         for log2, cand in lists.items():
             m = len(cand)
             if not m:
@@ -727,6 +731,19 @@ class DecisionPicture:
                      ssd2=hv.zeros(m, np.uint32))
             plan["sizes"][log2] = g
             plan["table"][log2 - 2] = [g["cbf"].data_ptr(), g["ssd"].data_ptr(), g["stats"].data_ptr(), g["d_jobs"].data_ptr(), g["d_fin"].data_ptr()]
+            if self.residual_rates:
+                # a depth-0 candidate is a job of its own; the four depth-1 candidates of a unit lie one after the other: ONE job that walks them in z-order with the
+                # contexts running on, as the reference codes them -- each from the unit's snapshot, like the RDOQ jobs
+                lead = np.flatnonzero(c[:, 2] == 0)
+                qj = np.zeros(len(lead), hmod.RESIDUAL_RATE_JOB_DT)
+                qj["level_off"], qj["rate_index"], qj["ctx_index"] = jobs[lead, 0], lead, u["ctx_index"][c[lead, 0]]
+                qj["sdh"], qj["count"] = 1, np.where(c[lead, 1] == 1, 4, 1)
+                with torch.cuda.stream(hv.tstream):
+                    g["d_qj"] = torch.from_numpy(qj.view(np.uint8).reshape(-1).copy()).to(hv.device)
+                    g["rates"] = torch.zeros(m, dtype=torch.int64, device=hv.device)
+                g["rate_jobs"] = qj
+                plan["table"][log2 - 2, 2] = 0      # (no level statistics: nonzero / sum_abs of the results are 0)
+                plan["rates"][log2 - 2] = g["rates"].data_ptr()
             plan["launches"] += 5
         plan["launches"] += 1
         # a block-sized area nobody reads, inside the reconstruction's bottom border (rewritten by the padding that ends the step): where the candidates that lost go
@@ -837,8 +854,15 @@ class DecisionPicture:
             hv.tu_forward_d(bd, 0, g["log2"], g["coef"], src, self.stride, self.pred, self.W, g["d_jobs"].view(-1, 4))
             hv.rdoq_d(bd, g["log2"], g["level"], g["coef"], self.d_states, g["d_rj"], g["cbf"], g["work"])
             hv.tu_reconstruct_d(bd, 0, g["log2"], g["inv"], g["dshift"], g["piece"], g["nn"], self.pred, self.W, src, self.stride, g["level"], g["d_jobs"].view(-1, 4), g["ssd"])
-            hv.level_stats_d(g["level"], g["d_sj"], g["m"], g["stats"])
-        hv.rqt_decide_d(P["d_units"].view(-1, 4), P["d_zero_at"], P["d_one_at"], P["table"], self.origin, self.stride, P["dump"], P["rl_q16"], P["d_out"])
+            if self.residual_rates:
+                hv.residual_rate_d(g["log2"], g["level"], self.d_states, g["d_qj"], g["rates"])
+            else:
+                hv.level_stats_d(g["level"], g["d_sj"], g["m"], g["stats"])
+        if self.residual_rates:
+            self._rqt_rates = None
+            hv.rqt_decide_rated_d(P["d_units"].view(-1, 4), P["d_zero_at"], P["d_one_at"], P["table"], P["rates"], self.origin, self.stride, P["dump"], P["rl_q16"], P["d_out"])
+        else:
+            hv.rqt_decide_d(P["d_units"].view(-1, 4), P["d_zero_at"], P["d_one_at"], P["table"], self.origin, self.stride, P["dump"], P["rl_q16"], P["d_out"])
         for g in P["sizes"].values():
             hv.tu_reconstruct_d(bd, 0, g["log2"], g["inv"], g["dshift"], self.recon, self.stride, self.pred, self.W, src, self.stride, g["level"], g["d_fin"].view(-1, 4), g["ssd2"])
         return P
@@ -853,6 +877,16 @@ class DecisionPicture:
     @rqt_results.setter
     def rqt_results(self, v):
         self._rqt = v
+
+    @property
+    def rqt_rates(self):
+        """residual_rates=True: {log2: int64 Q16 rate of every candidate of that transform size} of the last step (the order of rqt_plan["sizes"][log2]'s jobs):
+        downloaded when asked for"""
+        if not self.residual_rates:
+            raise ValueError("rqt_rates: the picture was made without residual_rates=True")
+        if getattr(self, "_rqt_rates", None) is None:
+            self._rqt_rates = {log2: self.hv.down(g["rates"], np.int64).copy() for log2, g in self.rqt_plan["sizes"].items()}
+        return self._rqt_rates
 
     @property
     def cells(self):
@@ -966,7 +1000,7 @@ class DecisionPicture:
         if self.search_on_device:
             # everything after the searches is a FIXED sequence of launches over device-resident tables (the decided field never leaves the device, the decisions
             # between the launches are kernels): recorded once into a HIP graph, one launch per picture, one wait at the end
-            self._rqt = self._cells = self._sao_decisions = None
+            self._rqt = self._cells = self._sao_decisions = self._rqt_rates = None
             if self.sao:
                 self._replayed("after the searches", lambda: (self.merge_candidates(field), self.predict(field), self.sao_filter_inputs(field),
                                                               self.sao_loop_filter()))
@@ -1027,6 +1061,8 @@ class DecisionPicture:
         hv, torch, W, H = self.hv, self.torch, self.W, self.H
         if not self.search_on_device:
             raise ValueError("step_banded needs the device search")
+        if self.residual_rates:
+            raise ValueError("step_banded does not price residuals with CABAC rates: use step() with residual_rates=True")
         if self.sao:
             # SAO of band b reads the deblocked rows of band b + 1 (turing/TaskSao.cpp:46-56): not built
             raise ValueError("step_banded does not run SAO: use step() with sao=True")

@@ -127,6 +127,8 @@ def _load():
         "rdoq": [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, C.c_size_t],
         "tu_forward_scan": [_vp, _i, _i, _i, _vp, _vp, _ip, _vp, _ip, _vp, _i, _vp, _vp, _vp, C.c_size_t],
         "rdoq_prescanned": [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, C.c_size_t],
+        "residual_rate": [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp],
+        "rqt_decide_rated": [_vp, _vp, _i, _vp, _vp, _vp, _vp, C.c_int64, C.c_ssize_t, _i, _i, _vp],
         "sao_stats": [_vp, _i, _i, _vp, _ip, _vp, _ip, _vp, _i, _vp],
         "sao_filter": [_vp, _i, _i, _vp, _ip, _vp, _ip, _vp, _i],
         "sao_band_chroma": [_vp, _i, _i, _vp, _ip, _vp, _ip, _vp, _i, _vp],
@@ -283,6 +285,12 @@ RDOQ_JOB_DT = np.dtype([("dst_off", "<i4"), ("src_off", "<i4"), ("quant_scale", 
                         ("lambda_q16", "<i4"), ("sdh_factor", "<i4"), ("ctx_index", "<i4"), ("c_idx", "u1"), ("scan_idx", "u1"),
                         ("is_intra", "u1"), ("sdh", "u1"), ("reserved", "<i4", 3)])
 assert RDOQ_JOB_DT.itemsize == 48
+
+
+# one havoc_mi355x_residual_rate_job (include/havoc_mi355x.h), 32 bytes
+RESIDUAL_RATE_JOB_DT = np.dtype([("level_off", "<i4"), ("ctx_index", "<i4"), ("rate_index", "<i4"), ("c_idx", "u1"), ("scan_idx", "u1"), ("sdh", "u1"), ("count", "u1"),
+                                 ("reserved", "<i4", 4)])
+assert RESIDUAL_RATE_JOB_DT.itemsize == 32
 
 
 def rdoq_lambda(lam, inv_scale):
@@ -511,6 +519,12 @@ class Havoc:
         """sizes: numpy uint64 [4, 5] of device addresses (d_cbf, d_ssd, d_stats, d_jobs, d_final) per transform size 4, 8, 16, 32"""
         self._ck(self.L.havoc_mi355x_rqt_decide(self.h, _ptr(units), units.shape[0], _ptr(zero_at), _ptr(one_at), sizes.ctypes.data, int(rec_origin), int(rec_stride), int(dump_off),
                                                 int(rl_q16), _ptr(out)))
+
+    def rqt_decide_rated_d(self, units, zero_at, one_at, sizes, rates, rec_origin, rec_stride, dump_off, rl_q16, out):
+        """rqt_decide_d with the residual term supplied: rates = numpy uint64 [4] of device addresses, the int64 Q16 rate of candidate j of each transform size
+        (residual_rate_d); the d_stats column of `sizes` may be 0"""
+        self._ck(self.L.havoc_mi355x_rqt_decide_rated(self.h, _ptr(units), units.shape[0], _ptr(zero_at), _ptr(one_at), sizes.ctypes.data, rates.ctypes.data, int(rec_origin),
+                                                      int(rec_stride), int(dump_off), int(rl_q16), _ptr(out)))
 
     def block_cells_add_d(self, width, height, qp, dpb_index0, field, units, decisions, cells):
         """the cells of `units` into cells that keep what they hold elsewhere (havoc_mi355x_block_cells_add)"""
@@ -839,6 +853,25 @@ class Havoc:
             j = self.torch.from_numpy(jobs.view(np.uint8).reshape(-1)).to(self.device)
         self.rdoq_d(bd, log2, dst, self.up(src), st, j, cbf, self.rdoq_workspace(len(jobs)))
         return self.down(dst, np.int16), self.down(cbf, np.int32)
+
+    def residual_rate_d(self, log2, levels, states, jobs, rates, states_out=None):
+        """the CABAC rate of residual_coding per block (havoc_mi355x_residual_rate); jobs: uint8 tensor holding RESIDUAL_RATE_JOB_DT records; rates: int64 tensor;
+        states_out: None, or a uint8 tensor of 128 bytes per job.  No sync."""
+        self._ck(self.L.havoc_mi355x_residual_rate(self.h, log2, _ptr(levels), _ptr(states), _ptr(jobs), jobs.numel() // RESIDUAL_RATE_JOB_DT.itemsize, _ptr(rates),
+                                                   _ptr(states_out)))
+
+    def residual_rate(self, log2, levels, states, jobs):
+        """numpy level: levels int16 (all blocks), states uint8 [k, 128], jobs RESIDUAL_RATE_JOB_DT array -> (rates int64 [max rate_index + count], the entries no
+        job writes 0; states_after uint8 [njobs, 128])"""
+        jobs = np.ascontiguousarray(jobs, RESIDUAL_RATE_JOB_DT)
+        nr = int((jobs["rate_index"].astype(np.int64) + np.clip(jobs["count"], 1, 4)).max()) if len(jobs) else 0
+        with self.torch.cuda.stream(self.tstream):
+            st = self.torch.from_numpy(np.ascontiguousarray(states, np.uint8).reshape(-1)).to(self.device)
+            j = self.torch.from_numpy(jobs.view(np.uint8).reshape(-1).copy()).to(self.device)
+            rates = self.torch.zeros(max(nr, 1), dtype=self.torch.int64, device=self.device)
+            after = self.torch.zeros(max(len(jobs), 1) * 128, dtype=self.torch.uint8, device=self.device)
+        self.residual_rate_d(log2, self.up(np.ascontiguousarray(levels, np.int16)), st, j, rates, after)
+        return self.down(rates, np.int64)[:nr], self.down(after, np.uint8)[:len(jobs) * 128].reshape(-1, 128)
 
     def ssd_linear_d(self, a, b, n, out):
         self._ck(self.L.havoc_mi355x_ssd_linear(self.h, _ptr(a), _ptr(b), n, _ptr(out)))

@@ -7,9 +7,12 @@
 //               evaluated too and the cheaper of  rate + (ssd0 + 4 ssd1 + 4 ssd2) * reciprocalLambda  wins, depth 0 on `<`.
 // Luma only here (the chroma blocks of the unit follow the luma tree and add 4 x their SSD: the havoc calls are the same).
 //
-// The RATE term is the entropy coder's estimate of the coded tree (EstimateRate<residual_coding>, turing/EstimateRate.h), which is CABAC and
-// out of this repository's scope: `tuRate` below is a STAND-IN with the same inputs' summary (coded flag, number and magnitude of the
-// levels), the same in every arm of the tests.  What is restated -- and checked against the reference's tables + Rdoq.cpp -- is the
+// The RATE term is the entropy coder's estimate of the coded tree (EstimateRate<residual_coding>, turing/EstimateRate.h).  `tuRate` below is a
+// STAND-IN with the same inputs' summary (coded flag, number and magnitude of the levels), the same in every arm of the tests; it is what the
+// host clients of this header and havoc_mi355x_rqt_decide use.  The RESIDUAL part of the term can now be the reference's: havoc_mi355x_residual_rate
+// measures residual_coding's CABAC bits per transform block on the device, bit for bit, and havoc_mi355x_rqt_decide_rated takes them in place of
+// `tuRate` (DecisionPicture(residual_rates=True)).  Still not priced anywhere: cbf_luma, split_transform_flag, the chroma residuals of the tree,
+// and the intra mode bits in their CABAC state.  What is restated here -- and checked against the reference's tables + Rdoq.cpp -- is the
 // order of evaluation, the uncoded short-cut, the cost arithmetic (Q16) and the strict comparison.
 #pragma once
 
