@@ -1,82 +1,10 @@
 // C ABI of libhavoc_mi355x.so (include/havoc_mi355x.h): context management, argument validation, launches.
 // There is no CPU path in this library: without a gfx950 device havoc_mi355x_create fails with ENODEV.
 #include "common.h"
+#include "launch.h"
 
 #include <cstdio>
 #include <cstring>
-
-namespace havoc_gpu {
-hipError_t launch_sad(hipStream_t, int S, int ways, const void *, long, const void *, long, const void *, int, int32_t *);
-hipError_t launch_sad_surface(hipStream_t, int S, int range, int maxw, int maxh, const void *, long, const void *, long, const void *, int, int32_t *);
-hipError_t launch_ssd(hipStream_t, int S, const void *, long, const void *, long, const void *, int, uint32_t *);
-hipError_t launch_satd(hipStream_t, int S, int maxw, int maxh, const void *, long, const void *, long, const void *, int, int32_t *);
-hipError_t launch_satd_multi(hipStream_t, int S, int maxw, int maxh, const void *, long, const void *, long, const void *, int, int32_t *);
-hipError_t launch_pad_block(hipStream_t, int S, void *, long, int, int, long, int, int, int, int, int);
-hipError_t launch_ssd_linear(hipStream_t, const uint8_t *, const uint8_t *, int, int32_t *);
-hipError_t launch_derive_bs(hipStream_t, const void *, long, int, int, int8_t *, uint8_t *);
-hipError_t launch_deblock(hipStream_t, int S, int bd, void *, long, void *, void *, long, int, int, const int8_t *, const uint8_t *, int, int, int, int);
-hipError_t launch_pred_uni(hipStream_t, int S, int taps, int bd, int maxw, int maxh, void *, long, const void *, long, const void *, int);
-hipError_t launch_pred_bi(hipStream_t, int S, int taps, int bd, int maxw, int maxh, void *, long, const void *, long, const void *, int);
-hipError_t launch_subtract_bi(hipStream_t, int S, int bd, void *, long, const void *, long, const void *, long, const void *, int);
-hipError_t launch_pred_classes(hipStream_t, int bi, int S, int taps, int bd, void *, long, const void *, long, const void *, const int count[4]);
-hipError_t launch_intra(hipStream_t, int S, int log2, int bd, void *, long, const void *, const void *, int);
-hipError_t launch_intra_satd35(hipStream_t, int S, int log2, int bd, const void *, long, const void *, const void *, int, int32_t *);
-hipError_t launch_sad4_runs(hipStream_t, int S, const void *, long, const void *, long, const void *, int, const void *, int, int32_t *);
-hipError_t launch_interp_planes(hipStream_t, int S, int bd, void *, long, const void *, long, int, int, int, int);
-hipError_t launch_subpel_satd(hipStream_t, int S, int taps, int bd, int maxw, int maxh, const void *, long, const void *, long, const void *, int,
-                              int32_t *);
-hipError_t launch_transform(hipStream_t, int bd, int log2, int tr, int16_t *, const int16_t *, long, const void *, int);
-hipError_t launch_inverse_transform(hipStream_t, int mode, int bd, int log2, int tr, void *, long, const void *, long, int16_t *, const int16_t *,
-                                    const void *, int);
-hipError_t launch_tu_forward(hipStream_t, int S, int bd, int log2, int tr, int16_t *, const void *, long, const void *, long, const void *, int);
-hipError_t launch_intra_measure(hipStream_t, int S, int bd, int log2, int16_t *, int16_t *, int32_t *, void *, uint32_t *, const void *, long, const void *, long, const void *, int, int);
-hipError_t launch_tu_forward_scan(hipStream_t, int S, int bd, int log2, int16_t *, const void *, long, const void *, long, const void *, int, const void *, int16_t *,
-                                  void *);
-hipError_t launch_rdoq_prescanned(hipStream_t, int bitDepth, int log2, int16_t *, const int16_t *, const uint8_t *, const void *, int, int32_t *, void *);
-hipError_t launch_tu_reconstruct(hipStream_t, int S, int bd, int log2, int tr, int scale, int shift, void *, long, const void *, long, const void *,
-                                 long, const int16_t *, const void *, int, uint32_t *);
-hipError_t launch_quantize(hipStream_t, int16_t *, const int16_t *, const void *, int, int32_t *);
-hipError_t launch_level_stats(hipStream_t, const int16_t *, const void *, int, int32_t *);
-hipError_t launch_intra_order(hipStream_t, const int32_t *, const void *, int, int32_t, int32_t *, int32_t *, int32_t *, int32_t *);
-hipError_t launch_intra_expand(hipStream_t, const void *, const int32_t *, const int32_t *, const int32_t *, const int32_t *, int, int, int, int, int, int, int, int, void *, void *,
-                               void *, int32_t *, int32_t *);
-hipError_t launch_intra_decide(hipStream_t, const void *, const int32_t *, const int32_t *, const int32_t *, const int32_t *, const uint32_t *, const int32_t *, const void *, int,
-                               int, int32_t, void *, void *);
-hipError_t launch_merge_jobs(hipStream_t, const void *, const int16_t *, const int32_t *, const int32_t *, int, int, void *, void *, void *, int16_t *);
-hipError_t launch_pred_jobs(hipStream_t, const void *, const int16_t *, int, const int32_t *, const int32_t *, int, int, int, const int32_t *, void *);
-hipError_t launch_rqt_decide(hipStream_t, const void *, int, const int32_t *, const int32_t *, const void *, long, int, int, int32_t, void *, const int64_t *const *rates);
-hipError_t launch_block_cells(hipStream_t, int, int, int, int, const int16_t *, const void *, const void *, int, void *, bool);
-hipError_t launch_search_wait_rows(hipStream_t, const void *, int, int, int, int *);
-hipError_t launch_intra_gather(hipStream_t, int, const void *, const void *, const int32_t *, const uint8_t *, const void *, int, const void *, void *, void *);
-hipError_t launch_intra_commit(hipStream_t, int, const void *, void *, uint8_t *, const void *, int, const void *, const void *, int);
-hipError_t launch_intra_fill_spare(hipStream_t, const int32_t *, int, int, void *, void *, void *, int32_t *, int32_t *);
-hipError_t launch_merge_decide(hipStream_t, const int32_t *, const int32_t *, const int32_t *, int, int64_t, int64_t *, int32_t *);
-size_t search_workspace_bytes(int width, int height);
-hipError_t launch_search_list(hipStream_t, int S, const havoc_mi355x_search_params *, const void *, long, long, const void *, long, long, const void *, long, long, const void *,
-                              int, void *);
-hipError_t launch_search_bi_list(hipStream_t, int S, const havoc_mi355x_search_params *, const void *, long, long, const void *, long, long, const void *, long, long, const void *,
-                                 long, const void *, const int16_t *, int, void *);
-hipError_t launch_search_picture_uni(hipStream_t, int S, const havoc_mi355x_search_params *, const int64_t *, const void *, long, long, const void *, const long *, long,
-                                     const void *, long, const long *, const void *, const int32_t *, int, int, int, void *, void *, int16_t *, void *, int, const int32_t *);
-hipError_t launch_rdoq(hipStream_t, int bd, int log2, int16_t *, const int16_t *, const uint8_t *, const void *, int, int32_t *, void *);
-size_t rdoq_workspace_bytes(int njobs);
-hipError_t launch_residual_rate(hipStream_t, int log2, const int16_t *, const uint8_t *, const void *, int, int64_t *, uint8_t *);
-hipError_t launch_sao_stats(hipStream_t, int S, int bd, const void *, long, const void *, long, const void *, int, int64_t *);
-hipError_t launch_sao_band_chroma(hipStream_t, int S, int bd, const void *, long, const void *, long, const void *, int, int64_t *);
-hipError_t launch_sao_filter(hipStream_t, int S, int bd, void *, long, const void *, long, const void *, int);
-size_t sao_workspace_bytes(int nctus);
-hipError_t launch_sao_estimate(hipStream_t, int S, int bd, double lambda, int flags, const void *, const void *, long, long, const void *, const void *, long, long,
-                               void *, void *, long, long, const void *, int, void *, void *);
-size_t sao_decide_workspace_bytes(int nctus);
-int sao_decide_max_row();
-hipError_t launch_sao_decide(hipStream_t, int S, int bd, long long lambda, int flags, const void *, const void *, long, long, const void *, const void *, long, long,
-                             void *, void *, long, long, const void *, int, int, const void *, int, int, void *, void *);
-hipError_t launch_sao_apply(hipStream_t, int S, int bd, int flags, int width, int height, int log2, const void *, const void *, const void *, long, long,
-                            void *, void *, void *, long, long, const void *, const void *, const int8_t *, long);
-hipError_t launch_quantize_inverse(hipStream_t, int16_t *, const int16_t *, const void *, int);
-hipError_t launch_quantize_reconstruct(hipStream_t, int log2, uint8_t *, long, const uint8_t *, long, const int16_t *, const void *, int);
-hipError_t launch_residual(hipStream_t, int S, int16_t *, long, const int32_t *, const void *, long, const void *, long, const void *, int);
-} // namespace havoc_gpu
 
 using namespace havoc_gpu;
 
@@ -92,13 +20,19 @@ static_assert(sizeof(havoc_mi355x_tu_job) == 16, "job ABI");
 static_assert(sizeof(havoc_mi355x_intra_search_job) == 32, "job ABI");
 static_assert(sizeof(havoc_mi355x_tu_fused_job) == 16, "job ABI");
 static_assert(sizeof(havoc_mi355x_quant_job) == 32, "job ABI");
-static_assert(sizeof(havoc_mi355x_sao_ctu) == 64 && sizeof(havoc_mi355x_sao_component) == 44 && sizeof(havoc_mi355x_sao_params) == 128, "sao record ABI");
+static_assert(sizeof(havoc_mi355x_sao_ctu) == 64 && sizeof(havoc_mi355x_sao_component) == 44 && sizeof(havoc_mi355x_sao_params) == 128 && sizeof(havoc_mi355x_sao_bounds) == 32,
+              "sao record ABI");
 static_assert(offsetof(havoc_mi355x_sao_params, dist_sao) == 88 && offsetof(havoc_mi355x_sao_params, ssd_sao) == 96 && offsetof(havoc_mi355x_sao_ctu, stat_src_cb) == 48,
               "sao record ABI");
 static_assert(sizeof(havoc_mi355x_sao_decision) == 128 && offsetof(havoc_mi355x_sao_decision, merge_left) == 88 &&
               offsetof(havoc_mi355x_sao_decision, ctx_merge_before) == 104 && offsetof(havoc_mi355x_sao_decision, decided) == 108, "sao record ABI");
 static_assert(sizeof(havoc_mi355x_residual_rate_job) == 32 && offsetof(havoc_mi355x_residual_rate_job, c_idx) == 12, "job ABI");
 static_assert(sizeof(havoc_mi355x_intra_mpm) == 40 && sizeof(havoc_mi355x_intra_choice) == 40, "job ABI");
+static_assert(sizeof(havoc_mi355x_rdoq_job) == 48 && offsetof(havoc_mi355x_rdoq_job, c_idx) == 32, "job ABI");
+static_assert(sizeof(havoc_mi355x_sad4_run) == 32 && sizeof(havoc_mi355x_sao_stats_job) == 16 && sizeof(havoc_mi355x_sao_chroma_job) == 32 && sizeof(havoc_mi355x_sao_job) == 96, "job ABI");
+static_assert(sizeof(havoc_mi355x_rqt_unit) == 16 && sizeof(havoc_mi355x_tu_outcome) == 16 && sizeof(havoc_mi355x_rqt_choice) == 104 && sizeof(havoc_mi355x_rqt_size) == 40 &&
+              sizeof(havoc_mi355x_cell) == 16 && offsetof(havoc_mi355x_cell, qp_y) == 11, "record ABI");
+static_assert(sizeof(havoc_mi355x_intra_chain_part) == 16 && sizeof(havoc_mi355x_intra_chain_layout) == 32 && sizeof(havoc_mi355x_field_layout) == 48, "record ABI");
 
 #include "ctx.h"
 
@@ -387,14 +321,14 @@ int havoc_mi355x_sad(havoc_mi355x_ctx *ctx, int S, const void *d_src, intptr_t s
                      const havoc_mi355x_pair_job *d_jobs, int njobs, int32_t *d_out)
 {
     REQUIRE_CTX(); REQUIRE_S(); REQUIRE(njobs >= 0, "njobs < 0");
-    return check(launch_sad(LS(ctx),S, 1, d_src, stride_src, d_ref, stride_ref, d_jobs, njobs, d_out), "sad");
+    return check(launch_sad(LS(ctx), S, d_src, stride_src, d_ref, stride_ref, d_jobs, njobs, d_out), "sad");
 }
 
 int havoc_mi355x_sad4(havoc_mi355x_ctx *ctx, int S, const void *d_src, intptr_t stride_src, const void *d_ref, intptr_t stride_ref,
                       const havoc_mi355x_sad4_job *d_jobs, int njobs, int32_t *d_out)
 {
     REQUIRE_CTX(); REQUIRE_S(); REQUIRE(njobs >= 0, "njobs < 0");
-    return check(launch_sad(LS(ctx),S, 4, d_src, stride_src, d_ref, stride_ref, d_jobs, njobs, d_out), "sad4");
+    return check(launch_sad4(LS(ctx), S, d_src, stride_src, d_ref, stride_ref, d_jobs, njobs, d_out), "sad4");
 }
 
 int havoc_mi355x_sad4_runs(havoc_mi355x_ctx *ctx, int S, const void *d_src, intptr_t stride_src, const void *d_ref, intptr_t stride_ref,
@@ -556,16 +490,14 @@ int havoc_mi355x_pred_uni_classes(havoc_mi355x_ctx *ctx, int S, int taps, int bi
                                   const havoc_mi355x_pred_uni_job *d_jobs, const int32_t count[4])
 {
     REQUIRE_CTX(); REQUIRE_S(); REQUIRE_BD(); REQUIRE(taps == 8 || taps == 4, "taps must be 8 or 4"); REQUIRE(count != nullptr, "null count");
-    const int c[4] = {count[0], count[1], count[2], count[3]};
-    return check(launch_pred_classes(LS(ctx), 0, S, taps, bitDepth, d_dst, stride_dst, d_ref, stride_ref, d_jobs, c), "pred_uni_classes");
+    return check(launch_pred_uni_classes(LS(ctx), S, taps, bitDepth, d_dst, stride_dst, d_ref, stride_ref, d_jobs, count), "pred_uni_classes");
 }
 
 int havoc_mi355x_pred_bi_classes(havoc_mi355x_ctx *ctx, int S, int taps, int bitDepth, void *d_dst, intptr_t stride_dst, const void *d_ref, intptr_t stride_ref,
                                  const havoc_mi355x_pred_bi_job *d_jobs, const int32_t count[4])
 {
     REQUIRE_CTX(); REQUIRE_S(); REQUIRE_BD(); REQUIRE(taps == 8 || taps == 4, "taps must be 8 or 4"); REQUIRE(count != nullptr, "null count");
-    const int c[4] = {count[0], count[1], count[2], count[3]};
-    return check(launch_pred_classes(LS(ctx), 1, S, taps, bitDepth, d_dst, stride_dst, d_ref, stride_ref, d_jobs, c), "pred_bi_classes");
+    return check(launch_pred_bi_classes(LS(ctx), S, taps, bitDepth, d_dst, stride_dst, d_ref, stride_ref, d_jobs, count), "pred_bi_classes");
 }
 
 int havoc_mi355x_subtract_bi(havoc_mi355x_ctx *ctx, int S, int bitDepth, void *d_dst, intptr_t stride_dst, const void *d_pred, intptr_t stride_pred,

@@ -14,25 +14,23 @@
 //                   caller's buffer.
 // The host forms of the same rules stay: they are what the per-call arms of the tests run over the reference's tables.
 #include "common.h"
+#include "launch.h"
 #include "../search/cand_mode_list.hpp"
 
 namespace havoc_gpu {
 
 namespace {
 
-struct IntraCtx { int32_t cand[3], neighbourModes, maxRefine, reserved; int64_t rateA, rateB; };                    // havoc_search_intra_ctx
-struct SearchJob { int32_t src_off, nb_off, nbf_off; uint32_t filt_lo, filt_hi; int32_t edge, reserved[2]; };       // havoc_mi355x_intra_search_job
-struct IntraJob { int32_t dst_off, nb_off, log2, mode, edge, reserved[3]; };                                          // havoc_mi355x_intra_job
-struct TuJob { int32_t coef_off, src_off, pred_off, rec_off; };                                                       // havoc_mi355x_tu_fused_job
-struct RdoqJobRec { int32_t dst_off, src_off, quant_scale, quant_shift, inv_scale, lambda_q16, sdh_factor, ctx_index; uint8_t c_idx, scan_idx, is_intra, sdh; int32_t reserved[3]; };
-struct RdResult { int32_t mode, index, evaluated, reserved; int64_t cost; int32_t cbf; uint32_t ssd; int32_t nonzero, sum_abs; };   // havoc_intra_rd_result
-static_assert(sizeof(IntraCtx) == 40 && sizeof(SearchJob) == 32 && sizeof(IntraJob) == 32 && sizeof(TuJob) == 16 && sizeof(RdoqJobRec) == 48 && sizeof(RdResult) == 40,
-              "record layouts");
+using IntraCtx = havoc_mi355x_intra_mpm;
+using SearchJob = havoc_mi355x_intra_search_job;
+using IntraJob = havoc_mi355x_intra_job;
+using TuJob = havoc_mi355x_tu_fused_job;
+using RdoqJob = havoc_mi355x_rdoq_job;
 
 constexpr int kMaxOrder = HAVOC_MI355X_INTRA_MAX_ORDER;      // maxRefine (<= 8) + 3 most probable modes, + 1 spare
 constexpr int64_t kCostMax = 0x7fffffffffffffffll;
 
-} // namespace
+} // namespace (the aliases name public types, so the kernels taking them have external linkage like the library's others; the mirrors made them internal)
 
 // order[i][0 .. count[i]) ; slot[i] = first candidate slot of partition i; total[0] = slots handed out, total[1] != 0: a partition wanted more
 // than kMaxOrder candidates
@@ -45,21 +43,21 @@ __global__ __launch_bounds__(64) void k_intra_order(const int32_t *__restrict__ 
     IntraCtx c = ictx[i];
     // the records come from device memory: a mode outside 0..34 or more than three neighbour modes would index past costs[] / cand[] -- flagged
     // (total[1] bit 1) and brought into range, so nothing is written outside the partition's own slots
-    const bool bad = (unsigned)c.cand[0] > 34u || (unsigned)c.cand[1] > 34u || (unsigned)c.cand[2] > 34u || (unsigned)c.neighbourModes > 3u || c.maxRefine < 1;
+    const bool bad = (unsigned)c.cand_mode_list[0] > 34u || (unsigned)c.cand_mode_list[1] > 34u || (unsigned)c.cand_mode_list[2] > 34u || (unsigned)c.neighbour_modes > 3u || c.max_refine < 1;
     if (bad)
     {
         atomicOr(total + 1, 2);
-        for (int k = 0; k < 3; ++k) c.cand[k] = min(max(c.cand[k], 0), 34);
-        c.neighbourModes = min(max(c.neighbourModes, 0), 3);
-        c.maxRefine = max(c.maxRefine, 1);
+        for (int k = 0; k < 3; ++k) c.cand_mode_list[k] = min(max(c.cand_mode_list[k], 0), 34);
+        c.neighbour_modes = min(max(c.neighbour_modes, 0), 3);
+        c.max_refine = max(c.max_refine, 1);
     }
     for (int m = 0; m < 35; ++m) costs[m][lane] = 0;
-    costs[c.cand[0]][lane] = c.rateA;
-    costs[c.cand[1]][lane] = c.rateB;
-    costs[c.cand[2]][lane] = c.rateB;
+    costs[c.cand_mode_list[0]][lane] = c.rate_a_minus_c;
+    costs[c.cand_mode_list[1]][lane] = c.rate_b_minus_c;
+    costs[c.cand_mode_list[2]][lane] = c.rate_b_minus_c;
     for (int m = 0; m < 35; ++m) costs[m][lane] += (int64_t)lambdaQ16 * (int64_t)satd35[35 * (long)i + m];
     int cnt = 0, nMpm = 0;
-    for (int j = 0; j < c.maxRefine + nMpm; ++j)
+    for (int j = 0; j < c.max_refine + nMpm; ++j)
     {
         if (cnt == kMaxOrder)      // more candidates than a partition has slots: reported, nothing written past them
         {
@@ -78,11 +76,11 @@ __global__ __launch_bounds__(64) void k_intra_order(const int32_t *__restrict__ 
             }
         }
         costs[mode][lane] = kCostMax;
-        if (j == c.maxRefine - 1)
-            for (int k = 0; k < c.neighbourModes; ++k)
-                if (costs[c.cand[k]][lane] != kCostMax)
+        if (j == c.max_refine - 1)
+            for (int k = 0; k < c.neighbour_modes; ++k)
+                if (costs[c.cand_mode_list[k]][lane] != kCostMax)
                 {
-                    costs[c.cand[k]][lane] = 0;
+                    costs[c.cand_mode_list[k]][lane] = 0;
                     ++nMpm;
                 }
         order[kMaxOrder * (long)i + cnt++] = mode;
@@ -94,7 +92,7 @@ __global__ __launch_bounds__(64) void k_intra_order(const int32_t *__restrict__ 
 __global__ __launch_bounds__(256) void k_intra_expand(const SearchJob *__restrict__ parts, const int32_t *__restrict__ order, const int32_t *__restrict__ count,
                                                       const int32_t *__restrict__ slot, const int32_t *__restrict__ ctxIndex, int n, int log2, int quantScale,
                                                       int quantShift, int invScale, int lambdaQ16, int sdhFactor, int sdh, IntraJob *__restrict__ ij,
-                                                      TuJob *__restrict__ tj, RdoqJobRec *__restrict__ rj, int32_t *__restrict__ sj, int32_t *__restrict__ owner)
+                                                      TuJob *__restrict__ tj, RdoqJob *__restrict__ rj, int32_t *__restrict__ sj, int32_t *__restrict__ owner)
 {
     const long t = blockIdx.x * 256L + threadIdx.x;
     const int i = (int)(t / kMaxOrder), k = (int)(t - (long)i * kMaxOrder);
@@ -106,7 +104,7 @@ __global__ __launch_bounds__(256) void k_intra_expand(const SearchJob *__restric
     ij[c] = a;
     TuJob b = {c * area, p.src_off, c * area, c * area};
     tj[c] = b;
-    RdoqJobRec r = {c * area, c * area, quantScale, quantShift, invScale, lambdaQ16, sdhFactor, ctxIndex[i], 0,
+    RdoqJob r = {c * area, c * area, quantScale, quantShift, invScale, lambdaQ16, sdhFactor, ctxIndex[i], 0,
                     (uint8_t)((log2 == 2 || log2 == 3) ? ((mode >= 6 && mode <= 14) ? 2 : ((mode >= 22 && mode <= 30) ? 1 : 0)) : 0), 1, (uint8_t)(sdh != 0), {0, 0, 0}};
     rj[c] = r;
     sj[2 * c] = c * area;
@@ -117,17 +115,17 @@ __global__ __launch_bounds__(256) void k_intra_expand(const SearchJob *__restric
 __global__ __launch_bounds__(256) void k_intra_decide(const IntraCtx *__restrict__ ictx, const int32_t *__restrict__ order, const int32_t *__restrict__ count,
                                                       const int32_t *__restrict__ slot, const int32_t *__restrict__ cbf, const uint32_t *__restrict__ ssd,
                                                       const int32_t *__restrict__ stats, const TuJob *__restrict__ tj, int n, int log2, int32_t reciprocalLambdaQ16,
-                                                      RdResult *__restrict__ out, TuJob *__restrict__ fin)
+                                                      havoc_mi355x_intra_choice *__restrict__ out, TuJob *__restrict__ fin)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const IntraCtx c = ictx[i];
-    RdResult r = {-1, 0, 0, 0, kCostMax, 0, 0, 0, 0};
+    havoc_mi355x_intra_choice r = {-1, 0, 0, 0, kCostMax, 0, 0, 0, 0};
     const int base = slot[i];
     for (int j = 0; j < count[i]; ++j)
     {
         const int mode = order[kMaxOrder * (long)i + j], s = base + j;
-        const int64_t modeRate = mode == c.cand[0] ? c.rateA : ((mode == c.cand[1] || mode == c.cand[2]) ? c.rateB : 0);
+        const int64_t modeRate = mode == c.cand_mode_list[0] ? c.rate_a_minus_c : ((mode == c.cand_mode_list[1] || mode == c.cand_mode_list[2]) ? c.rate_b_minus_c : 0);
         const int64_t tuRate = (int64_t)(1 + (cbf[s] ? 2 * stats[2 * s] + stats[2 * s + 1] : 0)) << 16;      // search/tu_decision.hpp: tuRate (stand-in; havoc_mi355x_residual_rate has the reference's residual bits, not used here yet)
         const int64_t cost = modeRate + tuRate + (int64_t)reciprocalLambdaQ16 * (int64_t)(int32_t)ssd[s];
         ++r.evaluated;
@@ -156,21 +154,20 @@ __global__ __launch_bounds__(256) void k_intra_decide(const IntraCtx *__restrict
 // between (the residual term is the stand-in of tu_decision.hpp, or -- RATED -- the reference's bits of each candidate's residual_coding from
 // kernels_residual_rate.hip; cbf_luma, split_transform_flag and the chroma residuals are priced by neither): the decision, the job records that reconstruct EVERY candidate -- the chosen ones into the picture, the others into a dump area (a fixed number of jobs per
 // size: the sequence can be recorded into a HIP graph) -- and the 4x4 cells havoc_mi355x_derive_bs reads.  The host forms stay: tests hold these against them.
-struct RqtUnit { int32_t x0, y0, log2, ctxIndex; };                                                                          // havoc_rqt_cu
-struct TuOutcome { int32_t cbf; uint32_t ssd; int32_t nonzero, sumAbs; };                                                    // havoc_tu_outcome
-struct RqtResult { int32_t depth, triedZero; TuOutcome zero, one[4]; int64_t costZero, costOne; };                            // havoc_rqt_result
-struct RqtSize { const int32_t *cbf; const uint32_t *ssd; const int32_t *stats; const TuJob *jobs; TuJob *fin; };             // one transform size: havoc_mi355x_rqt_size
+using RqtUnit = havoc_mi355x_rqt_unit;
+using TuOutcome = havoc_mi355x_tu_outcome;
+using RqtResult = havoc_mi355x_rqt_choice;
+using RqtSize = havoc_mi355x_rqt_size;      // one transform size
+using Cell = havoc_mi355x_cell;
 struct RqtSizes { RqtSize s[4]; };
-struct Cell { int16_t mv[2][2]; int8_t dpb[2]; uint8_t flags; int8_t qpY; uint8_t tuLog2; uint8_t reserved[3]; };            // havoc_mi355x_cell
-static_assert(sizeof(RqtUnit) == 16 && sizeof(TuOutcome) == 16 && sizeof(RqtResult) == 104 && sizeof(RqtSize) == 40 && sizeof(Cell) == 16, "record layouts");
 
 struct RqtRates { const int64_t *r[4]; };      // havoc_mi355x_rqt_decide_rated: the Q16 rate of candidate j of each transform size
 
 __device__ __forceinline__ TuOutcome outcomeOf(const RqtSize &z, int j)
 {
-    return z.stats ? TuOutcome{z.cbf[j], z.ssd[j], z.stats[2 * j], z.stats[2 * j + 1]} : TuOutcome{z.cbf[j], z.ssd[j], 0, 0};      // (no level statistics: the rated form)
+    return z.d_stats ? TuOutcome{z.d_cbf[j], z.d_ssd[j], z.d_stats[2 * j], z.d_stats[2 * j + 1]} : TuOutcome{z.d_cbf[j], z.d_ssd[j], 0, 0};      // (no level statistics: the rated form)
 }
-__device__ __forceinline__ int64_t tuRateOf(const TuOutcome &t) { return (int64_t)(1 + (t.cbf ? 2 * t.nonzero + t.sumAbs : 0)) << 16; }      // tu_decision.hpp: tuRate (stand-in)
+__device__ __forceinline__ int64_t tuRateOf(const TuOutcome &t) { return (int64_t)(1 + (t.cbf ? 2 * t.nonzero + t.sum_abs : 0)) << 16; }      // tu_decision.hpp: tuRate (stand-in)
 
 // RATED: the residual term is the caller's rate of each candidate (havoc_mi355x_residual_rate: the reference's bits) in place of the stand-in; nothing else differs
 template <bool RATED>
@@ -181,15 +178,15 @@ __global__ __launch_bounds__(256) void k_rqt_decide(const RqtUnit *__restrict__ 
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const RqtUnit u = units[i];
-    if (u.log2 < 3 || u.log2 > 5)      // a unit has a depth-0 block of 8 .. 32 and four depth-1 blocks of half that: anything else has no size table
+    if (u.log2_size < 3 || u.log2_size > 5)      // a unit has a depth-0 block of 8 .. 32 and four depth-1 blocks of half that: anything else has no size table
     {
         RqtResult bad = RqtResult();
         bad.depth = -1;
         out[i] = bad;
         return;
     }
-    const RqtSize &s0 = z.s[u.log2 - 2], &s1 = z.s[u.log2 - 3];
-    const int j0 = zeroAt[i], j1 = oneAt[i], half = 1 << (u.log2 - 1);
+    const RqtSize &s0 = z.s[u.log2_size - 2], &s1 = z.s[u.log2_size - 3];
+    const int j0 = zeroAt[i], j1 = oneAt[i], half = 1 << (u.log2_size - 1);
     RqtResult r = RqtResult();
     int32_t ssdOne = 0;      // (int32 as the reference's StateEncodeSubstream::ssd: four 16x16 blocks of <= 255^2 * 256 each, or 10-bit SSDs >> 4, stay far below 2^31)
     bool coded = false;
@@ -199,28 +196,28 @@ __global__ __launch_bounds__(256) void k_rqt_decide(const RqtUnit *__restrict__ 
         r.one[k] = outcomeOf(s1, j1 + k);
         ssdOne += (int32_t)r.one[k].ssd;
         coded |= r.one[k].cbf != 0;
-        rateOne += RATED ? rates.r[u.log2 - 3][j1 + k] : tuRateOf(r.one[k]);
+        rateOne += RATED ? rates.r[u.log2_size - 3][j1 + k] : tuRateOf(r.one[k]);
     }
-    r.costOne = rateOne + (int64_t)reciprocalLambdaQ16 * (int64_t)ssdOne;
+    r.cost_one = rateOne + (int64_t)reciprocalLambdaQ16 * (int64_t)ssdOne;
     if (coded)
     {
-        r.triedZero = 1;
+        r.tried_zero = 1;
         r.zero = outcomeOf(s0, j0);
-        r.costZero = (RATED ? rates.r[u.log2 - 2][j0] : tuRateOf(r.zero)) + (int64_t)reciprocalLambdaQ16 * (int64_t)(int32_t)r.zero.ssd;
-        r.depth = r.costZero < r.costOne ? 0 : 1;      // Reconstruct.cpp:1389
+        r.cost_zero = (RATED ? rates.r[u.log2_size - 2][j0] : tuRateOf(r.zero)) + (int64_t)reciprocalLambdaQ16 * (int64_t)(int32_t)r.zero.ssd;
+        r.depth = r.cost_zero < r.cost_one ? 0 : 1;      // Reconstruct.cpp:1389
     }
     out[i] = r;
     // every candidate is reconstructed once more: the chosen tree into the picture -- a unit left without residual through its four depth-1 blocks, whose levels are
     // all zero (= the prediction) -- the rest into the dump area
-    const bool zeroWins = r.depth == 0 && r.triedZero;
-    TuJob f = s0.jobs[j0];
+    const bool zeroWins = r.depth == 0 && r.tried_zero;
+    TuJob f = s0.d_jobs[j0];
     f.rec_off = zeroWins ? (int32_t)(recOrigin + (long)u.y0 * recStride + u.x0) : dumpOff;
-    s0.fin[j0] = f;
+    s0.d_final[j0] = f;
     for (int k = 0; k < 4; ++k)
     {
-        TuJob g = s1.jobs[j1 + k];
+        TuJob g = s1.d_jobs[j1 + k];
         g.rec_off = zeroWins ? dumpOff : (int32_t)(recOrigin + (long)(u.y0 + (k >> 1) * half) * recStride + u.x0 + (k & 1) * half);
-        s1.fin[j1 + k] = g;
+        s1.d_final[j1 + k] = g;
     }
 }
 
@@ -230,10 +227,10 @@ __global__ __launch_bounds__(256) void k_block_cells_blank(Cell *__restrict__ ce
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= count) return;
     Cell c = Cell();
-    c.dpb[0] = (int8_t)dpb0;
-    c.dpb[1] = -1;
-    c.qpY = (int8_t)qp;
-    c.tuLog2 = 2;
+    c.dpb_index[0] = (int8_t)dpb0;
+    c.dpb_index[1] = -1;
+    c.qp_y = (int8_t)qp;
+    c.tu_log2 = 2;
     cells[i] = c;
 }
 
@@ -243,46 +240,46 @@ __global__ __launch_bounds__(64) void k_block_cells(const RqtUnit *__restrict__ 
     const int i = blockIdx.x;
     if (i >= n) return;
     const RqtUnit u = units[i];
-    const int x4 = u.x0 >> 2, y4 = u.y0 >> 2, n4 = (1 << u.log2) >> 2, half = n4 >> 1;
+    const int x4 = u.x0 >> 2, y4 = u.y0 >> 2, n4 = (1 << u.log2_size) >> 2, half = n4 >> 1;
     const int32_t packed = field[(long)y4 * cw + x4];
     const RqtResult &d = dec[i];
-    const bool split = d.depth == 1, coded0 = d.triedZero == 1 && d.zero.cbf != 0;
+    const bool split = d.depth == 1, coded0 = d.tried_zero == 1 && d.zero.cbf != 0;
     for (int t = threadIdx.x; t < n4 * n4; t += 64)
     {
         const int y = t / n4, x = t - y * n4;
         Cell c = Cell();
         c.mv[0][0] = (int16_t)(packed & 0xffff);
         c.mv[0][1] = (int16_t)(packed >> 16);
-        c.dpb[0] = (int8_t)dpb0;
-        c.dpb[1] = -1;
-        c.qpY = (int8_t)qp;
+        c.dpb_index[0] = (int8_t)dpb0;
+        c.dpb_index[1] = -1;
+        c.qp_y = (int8_t)qp;
         const bool coded = split ? d.one[(y >= half) * 2 + (x >= half)].cbf != 0 : coded0;
         c.flags = (uint8_t)((coded ? 2 : 0) | (x == 0 ? 8 : 0) | (y == 0 ? 16 : 0));      // HAVOC_CELL_CODED, _PU_LEFT, _PU_TOP
-        c.tuLog2 = (uint8_t)(u.log2 - (split ? 1 : 0));
+        c.tu_log2 = (uint8_t)(u.log2_size - (split ? 1 : 0));
         cells[(long)(y4 + y) * cw + x4 + x] = c;
     }
 }
 
-hipError_t launch_rqt_decide(hipStream_t st, const void *units, int n, const int32_t *zeroAt, const int32_t *oneAt, const void *sizes, long recOrigin, int recStride, int dumpOff,
-                             int32_t rlQ16, void *out, const int64_t *const *rates)
+hipError_t launch_rqt_decide(hipStream_t st, const RqtUnit *units, int n, const int32_t *zeroAt, const int32_t *oneAt, const RqtSize sizes[4], long recOrigin, int recStride, int dumpOff,
+                             int32_t rlQ16, RqtResult *out, const int64_t *const *rates)
 {
     if (n <= 0) return hipSuccess;
+    const RqtSizes z{{sizes[0], sizes[1], sizes[2], sizes[3]}};
     if (rates)
-        hipLaunchKernelGGL(k_rqt_decide<true>, dim3((n + 255) / 256), dim3(256), 0, st, (const RqtUnit *)units, n, zeroAt, oneAt, *static_cast<const RqtSizes *>(sizes),
-                           RqtRates{{rates[0], rates[1], rates[2], rates[3]}}, recOrigin, recStride, dumpOff, rlQ16, (RqtResult *)out);
+        hipLaunchKernelGGL(k_rqt_decide<true>, dim3((n + 255) / 256), dim3(256), 0, st, units, n, zeroAt, oneAt, z,
+                           RqtRates{{rates[0], rates[1], rates[2], rates[3]}}, recOrigin, recStride, dumpOff, rlQ16, out);
     else
-        hipLaunchKernelGGL(k_rqt_decide<false>, dim3((n + 255) / 256), dim3(256), 0, st, (const RqtUnit *)units, n, zeroAt, oneAt, *static_cast<const RqtSizes *>(sizes),
-                           RqtRates(), recOrigin, recStride, dumpOff, rlQ16, (RqtResult *)out);
+        hipLaunchKernelGGL(k_rqt_decide<false>, dim3((n + 255) / 256), dim3(256), 0, st, units, n, zeroAt, oneAt, z, RqtRates(), recOrigin, recStride, dumpOff, rlQ16, out);
     return hipGetLastError();
 }
 
-hipError_t launch_block_cells(hipStream_t st, int width, int height, int qp, int dpb0, const int16_t *field, const void *units, const void *dec, int n, void *cells, bool blank)
+hipError_t launch_block_cells(hipStream_t st, int width, int height, int qp, int dpb0, const int16_t *field, const RqtUnit *units, const RqtResult *dec, int n, Cell *cells, bool blank)
 {
     const int cw = width >> 2, ch = height >> 2;
     if (blank)
-        hipLaunchKernelGGL(k_block_cells_blank, dim3((cw * ch + 255) / 256), dim3(256), 0, st, (Cell *)cells, cw * ch, qp, dpb0);
+        hipLaunchKernelGGL(k_block_cells_blank, dim3((cw * ch + 255) / 256), dim3(256), 0, st, cells, cw * ch, qp, dpb0);
     if (n > 0)
-        hipLaunchKernelGGL(k_block_cells, dim3(n), dim3(64), 0, st, (const RqtUnit *)units, (const RqtResult *)dec, n, reinterpret_cast<const int32_t *>(field), cw, qp, dpb0, (Cell *)cells);
+        hipLaunchKernelGGL(k_block_cells, dim3(n), dim3(64), 0, st, units, dec, n, reinterpret_cast<const int32_t *>(field), cw, qp, dpb0, cells);
     return hipGetLastError();
 }
 
@@ -294,9 +291,8 @@ hipError_t launch_block_cells(hipStream_t st, int width, int height, int qp, int
 //                    ones not yet coded / outside the picture (availability = "the 4x4 cell's owner precedes me in coding order"), their filtered copy ([1 2 1], or the bi-linear
 //                    strong smoothing of a flat 32x32 block's edges: IntraReferenceSamples.h:373-421), and candModeList from the modes decided left of and above it (CandModeList.h)
 //   k_intra_commit   per partition: the champion's reconstruction into the picture, its mode into the mode map
-struct ChainPart { int32_t x0, y0, log2, index; };                                                  // havoc_mi355x_intra_chain_part
-struct ChainLayout { int32_t picWidth, picHeight, stride, pad, cellsPerRow, bitDepth, ctbLog2, strongIntraSmoothing; };      // havoc_mi355x_intra_chain_layout
-static_assert(sizeof(ChainPart) == 16 && sizeof(ChainLayout) == 32, "record layouts");
+using ChainPart = havoc_mi355x_intra_chain_part;
+using ChainLayout = havoc_mi355x_intra_chain_layout;
 
 template <int S>
 __global__ __launch_bounds__(64) void k_intra_gather(const ChainLayout L, const char *__restrict__ recv, const int32_t *__restrict__ owner, const uint8_t *__restrict__ modes,
@@ -314,7 +310,7 @@ __global__ __launch_bounds__(64) void k_intra_gather(const ChainLayout L, const 
     T *nb = reinterpret_cast<T *>(nbv);
     const int nn = 1 << p.log2, len = 4 * nn + 1;
     auto available = [&](int x, int y) {
-        return x >= 0 && y >= 0 && x < L.picWidth && y < L.picHeight && owner[(y >> 2) * L.cellsPerRow + (x >> 2)] < p.index;
+        return x >= 0 && y >= 0 && x < L.pic_width && y < L.pic_height && owner[(y >> 2) * L.cells_per_row + (x >> 2)] < p.index;
     };
     for (int k = lane; k < len; k += 64)
     {   // k < 2n: the left column from the bottom; 2n: the corner; beyond: the row above
@@ -330,7 +326,7 @@ __global__ __launch_bounds__(64) void k_intra_gather(const ChainLayout L, const 
         int first = 0;
         while (first < len && !have[first]) ++first;
         if (first == len)
-            for (int k = 0; k < len; ++k) val[k] = 1 << (L.bitDepth - 1);
+            for (int k = 0; k < len; ++k) val[k] = 1 << (L.bit_depth - 1);
         else
         {
             if (first) val[0] = val[first];
@@ -342,8 +338,8 @@ __global__ __launch_bounds__(64) void k_intra_gather(const ChainLayout L, const 
     const long base = job.nb_off - (2 * nn + 1), basef = job.nbf_off - (2 * nn + 1);
     // IntraReferenceSamples.h:382-402 (HEVC 8.4.4.2.3): a 32x32 block whose two edges are nearly linear takes the bi-linear interpolation between the corner
     // and the ends instead of the [1 2 1] filter (strong_intra_smoothing_enabled_flag, on by default: Encoder.cpp:688)
-    const int corner = val[2 * nn], thr = 1 << (L.bitDepth - 5);
-    const bool strong = L.strongIntraSmoothing == 1 && nn == 32 && abs(corner + val[4 * nn] - 2 * val[3 * nn]) < thr && abs(corner + val[0] - 2 * val[nn]) < thr;
+    const int corner = val[2 * nn], thr = 1 << (L.bit_depth - 5);
+    const bool strong = L.strong_intra_smoothing == 1 && nn == 32 && abs(corner + val[4 * nn] - 2 * val[3 * nn]) < thr && abs(corner + val[0] - 2 * val[nn]) < thr;
     for (int k = lane; k < len; k += 64)
     {
         nb[base + k] = (T)val[k];
@@ -356,12 +352,12 @@ __global__ __launch_bounds__(64) void k_intra_gather(const ChainLayout L, const 
     }
     if (lane == 0)
     {   // CandModeList.h:33-95: A = left, B = above (DC when not there, or above in another CTU row)
-        const int a = available(p.x0 - 1, p.y0) ? modes[(p.y0 >> 2) * L.cellsPerRow + ((p.x0 - 1) >> 2)] : 1;
-        const int b = available(p.x0, p.y0 - 1) && (p.y0 - 1) >= ((p.y0 >> L.ctbLog2) << L.ctbLog2) ? modes[((p.y0 - 1) >> 2) * L.cellsPerRow + (p.x0 >> 2)] : 1;
+        const int a = available(p.x0 - 1, p.y0) ? modes[(p.y0 >> 2) * L.cells_per_row + ((p.x0 - 1) >> 2)] : 1;
+        const int b = available(p.x0, p.y0 - 1) && (p.y0 - 1) >= ((p.y0 >> L.ctb_log2) << L.ctb_log2) ? modes[((p.y0 - 1) >> 2) * L.cells_per_row + (p.x0 >> 2)] : 1;
         IntraCtx c = ictx[i];
         int cand[3];
-        c.neighbourModes = havoc_search::candModeListOf(a, b, cand);      // (search/cand_mode_list.hpp: pinned against the encoder's own lists)
-        c.cand[0] = cand[0]; c.cand[1] = cand[1]; c.cand[2] = cand[2];
+        c.neighbour_modes = havoc_search::candModeListOf(a, b, cand);      // (search/cand_mode_list.hpp: pinned against the encoder's own lists)
+        c.cand_mode_list[0] = cand[0]; c.cand_mode_list[1] = cand[1]; c.cand_mode_list[2] = cand[2];
         ictx[i] = c;
     }
 }
@@ -384,13 +380,13 @@ __global__ __launch_bounds__(256) void k_intra_commit(const ChainLayout L, char 
     }
     const int cw = nn >> 2, mode = choice[(long)i * choiceStride];      // a plain array of modes (stride 1) or the choice records (stride 10: `mode` leads)
     for (int t = threadIdx.x; t < cw * cw; t += 256)
-        modes[((p.y0 >> 2) + t / cw) * L.cellsPerRow + (p.x0 >> 2) + t % cw] = (uint8_t)mode;
+        modes[((p.y0 >> 2) + t / cw) * L.cells_per_row + (p.x0 >> 2) + t % cw] = (uint8_t)mode;
 }
 
 // the candidate slots [total[0], capacity) nobody was given: copies of slot 0's records that write into their OWN slots, so that the chain can be launched over
 // `capacity` jobs without the host first learning how many candidates there are (an intra picture's levels: thousands of small batches, no wait between them)
 __global__ __launch_bounds__(256) void k_intra_fill_spare(const int32_t *__restrict__ total, int capacity, int log2, IntraJob *__restrict__ ij, TuJob *__restrict__ tj,
-                                                          RdoqJobRec *__restrict__ rj, int32_t *__restrict__ sj, int32_t *__restrict__ owner)
+                                                          RdoqJob *__restrict__ rj, int32_t *__restrict__ sj, int32_t *__restrict__ owner)
 {
     const int c = total[0] + blockIdx.x * 256 + threadIdx.x;
     if (c >= capacity || total[0] <= 0) return;
@@ -400,7 +396,7 @@ __global__ __launch_bounds__(256) void k_intra_fill_spare(const int32_t *__restr
     ij[c] = a;
     const TuJob b = {c * area, tj[0].src_off, c * area, c * area};
     tj[c] = b;
-    RdoqJobRec r = rj[0];
+    RdoqJob r = rj[0];
     r.dst_off = r.src_off = c * area;
     rj[c] = r;
     sj[2 * c] = c * area;
@@ -408,29 +404,28 @@ __global__ __launch_bounds__(256) void k_intra_fill_spare(const int32_t *__restr
     owner[c] = owner[0];
 }
 
-hipError_t launch_intra_fill_spare(hipStream_t st, const int32_t *total, int capacity, int log2, void *ij, void *tj, void *rj, int32_t *sj, int32_t *owner)
+hipError_t launch_intra_fill_spare(hipStream_t st, const int32_t *total, int capacity, int log2, IntraJob *ij, TuJob *tj, RdoqJob *rj, int32_t *sj, int32_t *owner)
 {
     if (capacity <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_intra_fill_spare, dim3((capacity + 255) / 256), dim3(256), 0, st, total, capacity, log2, (IntraJob *)ij, (TuJob *)tj, (RdoqJobRec *)rj, sj, owner);
+    hipLaunchKernelGGL(k_intra_fill_spare, dim3((capacity + 255) / 256), dim3(256), 0, st, total, capacity, log2, ij, tj, rj, sj, owner);
     return hipGetLastError();
 }
 
-hipError_t launch_intra_gather(hipStream_t st, int S, const void *layout, const void *rec, const int32_t *owner, const uint8_t *modes, const void *parts, int n, const void *jobs,
-                               void *nb, void *ictx)
+hipError_t launch_intra_gather(hipStream_t st, int S, const ChainLayout *layout, const void *rec, const int32_t *owner, const uint8_t *modes, const ChainPart *parts, int n,
+                               const SearchJob *jobs, void *nb, IntraCtx *ictx)
 {
     if (n <= 0) return hipSuccess;
-    const ChainLayout L = *static_cast<const ChainLayout *>(layout);
-    if (S == 1) hipLaunchKernelGGL((k_intra_gather<1>), dim3(n), dim3(64), 0, st, L, (const char *)rec, owner, modes, (const ChainPart *)parts, n, (const SearchJob *)jobs, (char *)nb, (IntraCtx *)ictx);
-    else hipLaunchKernelGGL((k_intra_gather<2>), dim3(n), dim3(64), 0, st, L, (const char *)rec, owner, modes, (const ChainPart *)parts, n, (const SearchJob *)jobs, (char *)nb, (IntraCtx *)ictx);
+    if (S == 1) hipLaunchKernelGGL((k_intra_gather<1>), dim3(n), dim3(64), 0, st, *layout, (const char *)rec, owner, modes, parts, n, jobs, (char *)nb, ictx);
+    else hipLaunchKernelGGL((k_intra_gather<2>), dim3(n), dim3(64), 0, st, *layout, (const char *)rec, owner, modes, parts, n, jobs, (char *)nb, ictx);
     return hipGetLastError();
 }
 
-hipError_t launch_intra_commit(hipStream_t st, int S, const void *layout, void *rec, uint8_t *modes, const void *parts, int n, const void *blocks, const void *choice, int choiceStride)
+hipError_t launch_intra_commit(hipStream_t st, int S, const ChainLayout *layout, void *rec, uint8_t *modes, const ChainPart *parts, int n, const void *blocks, const int32_t *choice,
+                               int choiceStride)
 {
     if (n <= 0) return hipSuccess;
-    const ChainLayout L = *static_cast<const ChainLayout *>(layout);
-    if (S == 1) hipLaunchKernelGGL((k_intra_commit<1>), dim3(n), dim3(256), 0, st, L, (char *)rec, modes, (const ChainPart *)parts, n, (const char *)blocks, (const int32_t *)choice, choiceStride);
-    else hipLaunchKernelGGL((k_intra_commit<2>), dim3(n), dim3(256), 0, st, L, (char *)rec, modes, (const ChainPart *)parts, n, (const char *)blocks, (const int32_t *)choice, choiceStride);
+    if (S == 1) hipLaunchKernelGGL((k_intra_commit<1>), dim3(n), dim3(256), 0, st, *layout, (char *)rec, modes, parts, n, (const char *)blocks, choice, choiceStride);
+    else hipLaunchKernelGGL((k_intra_commit<2>), dim3(n), dim3(256), 0, st, *layout, (char *)rec, modes, parts, n, (const char *)blocks, choice, choiceStride);
     return hipGetLastError();
 }
 
@@ -439,15 +434,13 @@ hipError_t launch_intra_commit(hipStream_t st, int S, const void *layout, void *
 // candidates bi-directionally in three planes -- depend on the field the search kernel has just left in device memory; building them there keeps the
 // picture's step free of host work between its launches.  Layout of the pictures: planes of one component at multiples of `planeElems` (luma: source, list 0,
 // list 1; chroma: Cb source, list 0, list 1, then Cr source, list 0, list 1), `pad` samples of border, `stride` samples per row.
-struct MergeLayout { int32_t picWidth, picHeight, range, fieldCw, lumaStride, lumaPad, lumaPlaneElems, chromaStride, chromaPad, chromaPlaneElems, reserved[2]; };   // havoc_mi355x_field_layout
-struct PredUniJob { int32_t dst_off, ref_off, w, h, xFrac, yFrac, reserved[2]; };
-struct PredBiJob { int32_t dst_off, ref0_off, ref1_off, w, h, xFrac0, yFrac0, xFrac1, yFrac1, reserved[3]; };
-static_assert(sizeof(MergeLayout) == 48 && sizeof(PredUniJob) == 32 && sizeof(PredBiJob) == 48, "record layouts");
+using MergeLayout = havoc_mi355x_field_layout;
+using PredBiJob = havoc_mi355x_pred_bi_job;
 
 __device__ __forceinline__ void clampVector(const MergeLayout &L, int x0, int y0, int n, int &mx, int &my)
 {   // as LimitFullPelMv (Search.hpp:1366-1407) keeps the searches: the block stays within `range` samples of the picture (quarter-sample units)
-    mx = min(max(mx, (-L.range - x0) * 4), (L.picWidth + L.range - x0 - n) * 4);
-    my = min(max(my, (-L.range - y0) * 4), (L.picHeight + L.range - y0 - n) * 4);
+    mx = min(max(mx, (-L.range - x0) * 4), (L.pic_width + L.range - x0 - n) * 4);
+    my = min(max(my, (-L.range - y0) * 4), (L.pic_height + L.range - y0 - n) * 4);
 }
 
 // thread = (unit, candidate k of 5): the vectors of both lists at spatial merge position k (HEVC 8.5.3.2.3: A1, B1, B0, A0, B2; outside the picture: zero)
@@ -459,12 +452,12 @@ __global__ __launch_bounds__(256) void k_merge_jobs(const MergeLayout L, const i
     const int i = t / 5, k = t - 5 * i, nn = 1 << log2, x0 = ux[i], y0 = uy[i];
     const int px = k == 0 || k >= 3 ? x0 - 1 : (k == 1 ? x0 + nn - 1 : x0 + nn);
     const int py = k == 0 ? y0 + nn - 1 : (k == 3 ? y0 + nn : y0 - 1);
-    const bool inside = px >= 0 && py >= 0 && px < L.picWidth && py < L.picHeight;
-    const int ch = (L.picHeight + 3) >> 2;
+    const bool inside = px >= 0 && py >= 0 && px < L.pic_width && py < L.pic_height;
+    const int ch = (L.pic_height + 3) >> 2;
     int mv[2][2];
     for (int lst = 0; lst < 2; ++lst)
     {
-        const int32_t packed = inside ? field[((long)lst * ch + (py >> 2)) * L.fieldCw + (px >> 2)] : 0;
+        const int32_t packed = inside ? field[((long)lst * ch + (py >> 2)) * L.field_cw + (px >> 2)] : 0;
         mv[lst][0] = (int16_t)(packed & 0xffff);
         mv[lst][1] = (int16_t)(packed >> 16);
         clampVector(L, x0, y0, nn, mv[lst][0], mv[lst][1]);
@@ -474,9 +467,9 @@ __global__ __launch_bounds__(256) void k_merge_jobs(const MergeLayout L, const i
         PredBiJob j = PredBiJob();
         j.dst_off = t * nn * nn;
         j.w = j.h = nn;
-        const int here = (y0 + L.lumaPad) * L.lumaStride + x0 + L.lumaPad;
-        j.ref0_off = 1 * L.lumaPlaneElems + here + (mv[0][1] >> 2) * L.lumaStride + (mv[0][0] >> 2);
-        j.ref1_off = 2 * L.lumaPlaneElems + here + (mv[1][1] >> 2) * L.lumaStride + (mv[1][0] >> 2);
+        const int here = (y0 + L.luma_pad) * L.luma_stride + x0 + L.luma_pad;
+        j.ref0_off = 1 * L.luma_plane_elems + here + (mv[0][1] >> 2) * L.luma_stride + (mv[0][0] >> 2);
+        j.ref1_off = 2 * L.luma_plane_elems + here + (mv[1][1] >> 2) * L.luma_stride + (mv[1][0] >> 2);
         j.xFrac0 = mv[0][0] & 3; j.yFrac0 = mv[0][1] & 3; j.xFrac1 = mv[1][0] & 3; j.yFrac1 = mv[1][1] & 3;
         jl[t] = j;
     }
@@ -486,9 +479,9 @@ __global__ __launch_bounds__(256) void k_merge_jobs(const MergeLayout L, const i
         const int cn = nn >> 1;
         j.dst_off = t * cn * cn;
         j.w = j.h = cn;
-        const int here = ((y0 >> 1) + L.chromaPad) * L.chromaStride + (x0 >> 1) + L.chromaPad;
-        j.ref0_off = (3 * comp + 1) * L.chromaPlaneElems + here + (mv[0][1] >> 3) * L.chromaStride + (mv[0][0] >> 3);
-        j.ref1_off = (3 * comp + 2) * L.chromaPlaneElems + here + (mv[1][1] >> 3) * L.chromaStride + (mv[1][0] >> 3);
+        const int here = ((y0 >> 1) + L.chroma_pad) * L.chroma_stride + (x0 >> 1) + L.chroma_pad;
+        j.ref0_off = (3 * comp + 1) * L.chroma_plane_elems + here + (mv[0][1] >> 3) * L.chroma_stride + (mv[0][0] >> 3);
+        j.ref1_off = (3 * comp + 2) * L.chroma_plane_elems + here + (mv[1][1] >> 3) * L.chroma_stride + (mv[1][0] >> 3);
         j.xFrac0 = mv[0][0] & 7; j.yFrac0 = mv[0][1] & 7; j.xFrac1 = mv[1][0] & 7; j.yFrac1 = mv[1][1] & 7;
         (comp ? jcr : jcb)[t] = j;
     }
@@ -496,25 +489,25 @@ __global__ __launch_bounds__(256) void k_merge_jobs(const MergeLayout L, const i
 
 // thread = unit: its HavocPredUni job at the vector decided for list `list` at its origin; plane 0 = luma (8-tap phases), 1 / 2 = Cb / Cr (eighth-sample phases)
 __global__ __launch_bounds__(256) void k_pred_jobs(const MergeLayout L, const int32_t *__restrict__ field, int list, const int32_t *__restrict__ ux, const int32_t *__restrict__ uy,
-                                                   int n, int log2, int plane, const int32_t *__restrict__ dstOff, PredUniJob *__restrict__ jobs)
+                                                   int n, int log2, int plane, const int32_t *__restrict__ dstOff, havoc_mi355x_pred_uni_job *__restrict__ jobs)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const int x0 = ux[i], y0 = uy[i], ch = (L.picHeight + 3) >> 2;
-    const int32_t packed = field[((long)list * ch + (y0 >> 2)) * L.fieldCw + (x0 >> 2)];
+    const int x0 = ux[i], y0 = uy[i], ch = (L.pic_height + 3) >> 2;
+    const int32_t packed = field[((long)list * ch + (y0 >> 2)) * L.field_cw + (x0 >> 2)];
     const int mx = (int16_t)(packed & 0xffff), my = (int16_t)(packed >> 16);
-    PredUniJob j = PredUniJob();
+    havoc_mi355x_pred_uni_job j = havoc_mi355x_pred_uni_job();
     j.dst_off = dstOff[i];
     if (plane == 0)
     {
         j.w = j.h = 1 << log2;
-        j.ref_off = (1 + list) * L.lumaPlaneElems + (y0 + (my >> 2) + L.lumaPad) * L.lumaStride + x0 + (mx >> 2) + L.lumaPad;
+        j.ref_off = (1 + list) * L.luma_plane_elems + (y0 + (my >> 2) + L.luma_pad) * L.luma_stride + x0 + (mx >> 2) + L.luma_pad;
         j.xFrac = mx & 3; j.yFrac = my & 3;
     }
     else
     {
         j.w = j.h = 1 << (log2 - 1);
-        j.ref_off = (3 * (plane - 1) + 1 + list) * L.chromaPlaneElems + ((y0 >> 1) + (my >> 3) + L.chromaPad) * L.chromaStride + (x0 >> 1) + (mx >> 3) + L.chromaPad;
+        j.ref_off = (3 * (plane - 1) + 1 + list) * L.chroma_plane_elems + ((y0 >> 1) + (my >> 3) + L.chroma_pad) * L.chroma_stride + (x0 >> 1) + (mx >> 3) + L.chroma_pad;
         j.xFrac = mx & 7; j.yFrac = my & 7;
     }
     jobs[i] = j;
@@ -546,50 +539,49 @@ hipError_t launch_merge_decide(hipStream_t st, const int32_t *sy, const int32_t 
     return hipGetLastError();
 }
 
-hipError_t launch_merge_jobs(hipStream_t st, const void *layout, const int16_t *field, const int32_t *ux, const int32_t *uy, int n, int log2, void *jl, void *jcb, void *jcr,
+hipError_t launch_merge_jobs(hipStream_t st, const MergeLayout *layout, const int16_t *field, const int32_t *ux, const int32_t *uy, int n, int log2, PredBiJob *jl, PredBiJob *jcb, PredBiJob *jcr,
                              int16_t *vectors)
 {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_merge_jobs, dim3((5 * n + 255) / 256), dim3(256), 0, st, *static_cast<const MergeLayout *>(layout), reinterpret_cast<const int32_t *>(field), ux, uy, n, log2,
-                       (PredBiJob *)jl, (PredBiJob *)jcb, (PredBiJob *)jcr, reinterpret_cast<int32_t *>(vectors));
+    hipLaunchKernelGGL(k_merge_jobs, dim3((5 * n + 255) / 256), dim3(256), 0, st, *layout, reinterpret_cast<const int32_t *>(field), ux, uy, n, log2, jl, jcb, jcr,
+                       reinterpret_cast<int32_t *>(vectors));
     return hipGetLastError();
 }
 
-hipError_t launch_pred_jobs(hipStream_t st, const void *layout, const int16_t *field, int list, const int32_t *ux, const int32_t *uy, int n, int log2, int plane,
-                            const int32_t *dstOff, void *jobs)
+hipError_t launch_pred_jobs(hipStream_t st, const MergeLayout *layout, const int16_t *field, int list, const int32_t *ux, const int32_t *uy, int n, int log2, int plane,
+                            const int32_t *dstOff, havoc_mi355x_pred_uni_job *jobs)
 {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_pred_jobs, dim3((n + 255) / 256), dim3(256), 0, st, *static_cast<const MergeLayout *>(layout), reinterpret_cast<const int32_t *>(field), list, ux, uy, n, log2,
-                       plane, dstOff, (PredUniJob *)jobs);
+    hipLaunchKernelGGL(k_pred_jobs, dim3((n + 255) / 256), dim3(256), 0, st, *layout, reinterpret_cast<const int32_t *>(field), list, ux, uy, n, log2, plane, dstOff, jobs);
     return hipGetLastError();
 }
 
-hipError_t launch_intra_order(hipStream_t st, const int32_t *satd35, const void *ictx, int n, int32_t lambdaQ16, int32_t *order, int32_t *count, int32_t *slot,
+hipError_t launch_intra_order(hipStream_t st, const int32_t *satd35, const IntraCtx *ictx, int n, int32_t lambdaQ16, int32_t *order, int32_t *count, int32_t *slot,
                               int32_t *total)
 {
     if (n <= 0) return hipSuccess;
     hipError_t e = hipMemsetAsync(total, 0, 8, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_intra_order, dim3((n + 63) / 64), dim3(64), 0, st, satd35, (const IntraCtx *)ictx, n, lambdaQ16, order, count, slot, total);
+    hipLaunchKernelGGL(k_intra_order, dim3((n + 63) / 64), dim3(64), 0, st, satd35, ictx, n, lambdaQ16, order, count, slot, total);
     return hipGetLastError();
 }
 
-hipError_t launch_intra_expand(hipStream_t st, const void *parts, const int32_t *order, const int32_t *count, const int32_t *slot, const int32_t *ctxIndex, int n, int log2,
-                               int quantScale, int quantShift, int invScale, int lambdaQ16, int sdhFactor, int sdh, void *ij, void *tj, void *rj, int32_t *sj, int32_t *owner)
+hipError_t launch_intra_expand(hipStream_t st, const SearchJob *parts, const int32_t *order, const int32_t *count, const int32_t *slot, const int32_t *ctxIndex, int n, int log2,
+                               int quantScale, int quantShift, int invScale, int lambdaQ16, int sdhFactor, int sdh, IntraJob *ij, TuJob *tj, RdoqJob *rj, int32_t *sj,
+                               int32_t *owner)
 {
     if (n <= 0) return hipSuccess;
     const long threads = (long)n * kMaxOrder;
-    hipLaunchKernelGGL(k_intra_expand, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, (const SearchJob *)parts, order, count, slot, ctxIndex, n, log2, quantScale,
-                       quantShift, invScale, lambdaQ16, sdhFactor, sdh, (IntraJob *)ij, (TuJob *)tj, (RdoqJobRec *)rj, sj, owner);
+    hipLaunchKernelGGL(k_intra_expand, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, parts, order, count, slot, ctxIndex, n, log2, quantScale,
+                       quantShift, invScale, lambdaQ16, sdhFactor, sdh, ij, tj, rj, sj, owner);
     return hipGetLastError();
 }
 
-hipError_t launch_intra_decide(hipStream_t st, const void *ictx, const int32_t *order, const int32_t *count, const int32_t *slot, const int32_t *cbf, const uint32_t *ssd,
-                               const int32_t *stats, const void *tj, int n, int log2, int32_t reciprocalLambdaQ16, void *out, void *fin)
+hipError_t launch_intra_decide(hipStream_t st, const IntraCtx *ictx, const int32_t *order, const int32_t *count, const int32_t *slot, const int32_t *cbf, const uint32_t *ssd,
+                               const int32_t *stats, const TuJob *tj, int n, int log2, int32_t reciprocalLambdaQ16, havoc_mi355x_intra_choice *out, TuJob *fin)
 {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_intra_decide, dim3((n + 255) / 256), dim3(256), 0, st, (const IntraCtx *)ictx, order, count, slot, cbf, ssd, stats, (const TuJob *)tj, n, log2,
-                       reciprocalLambdaQ16, (RdResult *)out, (TuJob *)fin);
+    hipLaunchKernelGGL(k_intra_decide, dim3((n + 255) / 256), dim3(256), 0, st, ictx, order, count, slot, cbf, ssd, stats, tj, n, log2, reciprocalLambdaQ16, out, fin);
     return hipGetLastError();
 }
 

@@ -16,6 +16,7 @@
 // (scattered 16-bit reference reads conflict on banks) more than by VALU, hence the register-resident source tile,
 // the one-vector reference read per row and the rotation instead of a second read.
 #include "common.h"
+#include "launch.h"
 
 namespace havoc_gpu {
 
@@ -393,7 +394,7 @@ __global__ __launch_bounds__(THREADS) void k_intra_satd35(const char *__restrict
 }
 
 template <int S>
-static hipError_t launch_intra_satd35_s(hipStream_t st, int log2, int bitDepth, const void *src, long ss, const void *nb, const void *jobs, int n,
+static hipError_t launch_intra_satd35_s(hipStream_t st, int log2, int bitDepth, const void *src, long ss, const void *nb, const havoc_mi355x_intra_search_job *jobs, int n,
                                         int32_t *cost)
 {
     const char *s = (const char *)src, *q = (const char *)nb;
@@ -412,7 +413,7 @@ static hipError_t launch_intra_satd35_s(hipStream_t st, int log2, int bitDepth, 
     return hipGetLastError();
 }
 
-hipError_t launch_intra_satd35(hipStream_t st, int S, int log2, int bitDepth, const void *src, long ss, const void *nb, const void *jobs, int n,
+hipError_t launch_intra_satd35(hipStream_t st, int S, int log2, int bitDepth, const void *src, long ss, const void *nb, const havoc_mi355x_intra_search_job *jobs, int n,
                                int32_t *cost)
 {
     if (n <= 0) return hipSuccess;

@@ -14,6 +14,7 @@
 // the reference's table is indexed by width class: G = 8 / 32 / 128 / 256 lanes per block, 256 / G blocks per
 // workgroup.
 #include "common.h"
+#include "launch.h"
 #include "interp.h"
 
 namespace havoc_gpu {
@@ -218,12 +219,11 @@ static hipError_t launch_pred_st(hipStream_t st, int bd, int maxw, int maxh, cha
 
 template <bool BI>
 static hipError_t launch_pred(hipStream_t st, int S, int taps, int bd, int maxw, int maxh, void *dst, long sd, const void *ref, long sr,
-                              const void *jobs, int n)
+                              const int32_t *j, int n)
 {
     if (n <= 0) return hipSuccess;
     char *d = (char *)dst;
     const char *r = (const char *)ref;
-    const int32_t *j = (const int32_t *)jobs;
     if (S == 1 && taps == 8) return launch_pred_st<1, 8, BI>(st, bd, maxw, maxh, d, sd, r, sr, j, n);
     if (S == 1 && taps == 4) return launch_pred_st<1, 4, BI>(st, bd, maxw, maxh, d, sd, r, sr, j, n);
     if (S == 2 && taps == 8) return launch_pred_st<2, 8, BI>(st, bd, maxw, maxh, d, sd, r, sr, j, n);
@@ -232,19 +232,19 @@ static hipError_t launch_pred(hipStream_t st, int S, int taps, int bd, int maxw,
 }
 
 hipError_t launch_pred_uni(hipStream_t st, int S, int taps, int bd, int maxw, int maxh, void *dst, long sd, const void *ref, long sr,
-                           const void *jobs, int n)
+                           const havoc_mi355x_pred_uni_job *jobs, int n)
 {
-    return launch_pred<false>(st, S, taps, bd, maxw, maxh, dst, sd, ref, sr, jobs, n);
+    return launch_pred<false>(st, S, taps, bd, maxw, maxh, dst, sd, ref, sr, (const int32_t *)jobs, n);
 }
 
-hipError_t launch_pred_bi(hipStream_t st, int S, int taps, int bd, int maxw, int maxh, void *dst, long sd, const void *ref, long sr, const void *jobs,
-                          int n)
+hipError_t launch_pred_bi(hipStream_t st, int S, int taps, int bd, int maxw, int maxh, void *dst, long sd, const void *ref, long sr,
+                          const havoc_mi355x_pred_bi_job *jobs, int n)
 {
-    return launch_pred<true>(st, S, taps, bd, maxw, maxh, dst, sd, ref, sr, jobs, n);
+    return launch_pred<true>(st, S, taps, bd, maxw, maxh, dst, sd, ref, sr, (const int32_t *)jobs, n);
 }
 
 template <bool BI>
-static hipError_t launch_pred_classes_t(hipStream_t st, int S, int taps, int bd, void *dst, long sd, const void *ref, long sr, const void *jobs, const int count[4])
+static hipError_t launch_pred_classes_t(hipStream_t st, int S, int taps, int bd, void *dst, long sd, const void *ref, long sr, const int32_t *j, const int count[4])
 {
     PredClasses pc;
     static const int jpw[4] = {32, 8, 2, 1};
@@ -258,7 +258,6 @@ static hipError_t launch_pred_classes_t(hipStream_t st, int S, int taps, int bd,
     if (pc.firstWg[4] == 0) return hipSuccess;
     char *d = (char *)dst;
     const char *r = (const char *)ref;
-    const int32_t *j = (const int32_t *)jobs;
     const dim3 g(pc.firstWg[4]), b(256);
     if (S == 1 && taps == 8) hipLaunchKernelGGL((k_pred_classes<1, 8, BI>), g, b, 0, st, d, sd, r, sr, j, pc, bd);
     else if (S == 1 && taps == 4) hipLaunchKernelGGL((k_pred_classes<1, 4, BI>), g, b, 0, st, d, sd, r, sr, j, pc, bd);
@@ -268,13 +267,18 @@ static hipError_t launch_pred_classes_t(hipStream_t st, int S, int taps, int bd,
     return hipGetLastError();
 }
 
-hipError_t launch_pred_classes(hipStream_t st, int bi, int S, int taps, int bd, void *dst, long sd, const void *ref, long sr, const void *jobs, const int count[4])
+hipError_t launch_pred_bi_classes(hipStream_t st, int S, int taps, int bd, void *dst, long sd, const void *ref, long sr, const havoc_mi355x_pred_bi_job *jobs, const int count[4])
 {
-    return bi ? launch_pred_classes_t<true>(st, S, taps, bd, dst, sd, ref, sr, jobs, count) : launch_pred_classes_t<false>(st, S, taps, bd, dst, sd, ref, sr, jobs, count);
+    return launch_pred_classes_t<true>(st, S, taps, bd, dst, sd, ref, sr, (const int32_t *)jobs, count);
+}
+
+hipError_t launch_pred_uni_classes(hipStream_t st, int S, int taps, int bd, void *dst, long sd, const void *ref, long sr, const havoc_mi355x_pred_uni_job *jobs, const int count[4])
+{
+    return launch_pred_classes_t<false>(st, S, taps, bd, dst, sd, ref, sr, (const int32_t *)jobs, count);
 }
 
 hipError_t launch_subtract_bi(hipStream_t st, int S, int bitDepth, void *dst, long sd, const void *pred, long sp, const void *src, long ss,
-                              const void *jobs, int n)
+                              const havoc_mi355x_subtract_bi_job *jobs, int n)
 {
     if (n <= 0) return hipSuccess;
     if (S == 1)

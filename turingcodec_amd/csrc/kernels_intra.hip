@@ -6,6 +6,7 @@
 // samples), each producing 4x4 sub-blocks, so a wavefront carries 16 / 16 / 4 / 1 jobs.  The 4n+1 neighbour samples
 // and the projected angular reference array live in LDS; a line of four angular samples is two packed 16-bit lerps.
 #include "common.h"
+#include "launch.h"
 
 namespace havoc_gpu {
 
@@ -230,7 +231,7 @@ __global__ __launch_bounds__(64) void k_intra(char *__restrict__ dst, long strid
 }
 
 template <int S>
-static hipError_t launch_intra_s(hipStream_t st, int log2, int bitDepth, void *dst, long sd, const void *nb, const void *jobs, int n)
+static hipError_t launch_intra_s(hipStream_t st, int log2, int bitDepth, void *dst, long sd, const void *nb, const havoc_mi355x_intra_job *jobs, int n)
 {
     char *d = (char *)dst;
     const char *p = (const char *)nb;
@@ -248,7 +249,7 @@ static hipError_t launch_intra_s(hipStream_t st, int log2, int bitDepth, void *d
     return hipGetLastError();
 }
 
-hipError_t launch_intra(hipStream_t st, int S, int log2, int bitDepth, void *dst, long sd, const void *nb, const void *jobs, int n)
+hipError_t launch_intra(hipStream_t st, int S, int log2, int bitDepth, void *dst, long sd, const void *nb, const havoc_mi355x_intra_job *jobs, int n)
 {
     if (n <= 0) return hipSuccess;
     return S == 1 ? launch_intra_s<1>(st, log2, bitDepth, dst, sd, nb, jobs, n) : launch_intra_s<2>(st, log2, bitDepth, dst, sd, nb, jobs, n);

@@ -8,6 +8,7 @@
 // sums are folded with DPP row shifts / mirrors -- integer arithmetic only, no LDS, no MFMA.  Workgroup b takes the
 // b % 8-th contiguous eighth of the job table (xcd_block): one band of the picture per XCD L2.
 #include "common.h"
+#include "launch.h"
 
 #include <cstdlib>
 
@@ -1305,7 +1306,8 @@ static int sad4_run_waves()
     return v;
 }
 
-hipError_t launch_sad4_runs(hipStream_t st, int S, const void *src, long ss, const void *ref, long rs, const void *jobs, int n, const void *runs, int nruns, int32_t *out)
+hipError_t launch_sad4_runs(hipStream_t st, int S, const void *src, long ss, const void *ref, long rs, const havoc_mi355x_sad4_job *jobs, int n,
+                            const havoc_mi355x_sad4_run *runs, int nruns, int32_t *out)
 {
     if (n <= 0 || nruns <= 0) return hipSuccess;
     if (rs < 64 || rs >= (1 << 22) || (S != 1 && S != 2)) return hipErrorInvalidValue;
@@ -1327,11 +1329,10 @@ hipError_t launch_sad4_runs(hipStream_t st, int S, const void *src, long ss, con
     return hipGetLastError();
 }
 
-hipError_t launch_sad(hipStream_t st, int S, int ways, const void *src, long ss, const void *ref, long rs, const void *jobs, int n, int32_t *out)
+static hipError_t launch_sad_ways(hipStream_t st, int S, int ways, const void *src, long ss, const void *ref, long rs, const int32_t *j, int n, int32_t *out)
 {
     if (n <= 0) return hipSuccess;
     const char *s = (const char *)src, *r = (const char *)ref;
-    const int32_t *j = (const int32_t *)jobs;
     const dim3 g((n + 256 / kSadLanes - 1) / (256 / kSadLanes)), b(256);
     if (S == 1 && ways == 1) hipLaunchKernelGGL((k_sad<1, 1>), g, b, 0, st, s, ss, r, rs, j, n, out);
     else if (S == 2 && ways == 1) hipLaunchKernelGGL((k_sad<2, 1>), g, b, 0, st, s, ss, r, rs, j, n, out);
@@ -1349,7 +1350,17 @@ hipError_t launch_sad(hipStream_t st, int S, int ways, const void *src, long ss,
     return hipGetLastError();
 }
 
-hipError_t launch_ssd(hipStream_t st, int S, const void *a, long sa, const void *b, long sb, const void *jobs, int n, uint32_t *out)
+hipError_t launch_sad(hipStream_t st, int S, const void *src, long ss, const void *ref, long rs, const havoc_mi355x_pair_job *jobs, int n, int32_t *out)
+{
+    return launch_sad_ways(st, S, 1, src, ss, ref, rs, (const int32_t *)jobs, n, out);
+}
+
+hipError_t launch_sad4(hipStream_t st, int S, const void *src, long ss, const void *ref, long rs, const havoc_mi355x_sad4_job *jobs, int n, int32_t *out)
+{
+    return launch_sad_ways(st, S, 4, src, ss, ref, rs, (const int32_t *)jobs, n, out);
+}
+
+hipError_t launch_ssd(hipStream_t st, int S, const void *a, long sa, const void *b, long sb, const havoc_mi355x_pair_job *jobs, int n, uint32_t *out)
 {
     if (n <= 0) return hipSuccess;
     const dim3 g((n + 256 / kSadLanes - 1) / (256 / kSadLanes)), b256(256);   // 16 lanes per job
@@ -1358,8 +1369,8 @@ hipError_t launch_ssd(hipStream_t st, int S, const void *a, long sa, const void 
     return hipGetLastError();
 }
 
-hipError_t launch_satd(hipStream_t st, int S, int maxw, int maxh, const void *a, long sa, const void *b, long sb, const void *jobs, int n,
-                       int32_t *out)
+hipError_t launch_satd(hipStream_t st, int S, int maxw, int maxh, const void *a, long sa, const void *b, long sb, const havoc_mi355x_pair_job *jobs,
+                       int n, int32_t *out)
 {
     if (n <= 0) return hipSuccess;
     const char *x = (const char *)a, *y = (const char *)b;
@@ -1375,8 +1386,8 @@ hipError_t launch_satd(hipStream_t st, int S, int maxw, int maxh, const void *a,
     return hipGetLastError();
 }
 
-hipError_t launch_satd_multi(hipStream_t st, int S, int maxw, int maxh, const void *a, long sa, const void *b, long sb, const void *jobs, int n,
-                             int32_t *out)
+hipError_t launch_satd_multi(hipStream_t st, int S, int maxw, int maxh, const void *a, long sa, const void *b, long sb,
+                             const havoc_mi355x_satd_multi_job *jobs, int n, int32_t *out)
 {
     if (n <= 0) return hipSuccess;
     const char *x = (const char *)a, *y = (const char *)b;

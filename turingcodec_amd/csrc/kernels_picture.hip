@@ -7,6 +7,7 @@
 // (rows first, then copies of the padded first / last row) produce -- so no pass ordering is needed: one thread per
 // border sample, reading only the interior.
 #include "common.h"
+#include "launch.h"
 
 namespace havoc_gpu {
 
@@ -216,14 +217,13 @@ __global__ __launch_bounds__(256) void k_deblock(DeblockArgs a)
 }
 
 // ---- boundary strengths from the block structure (LoopFilter::Picture::processCu / Pu / Tu / Rc, turing/LoopFilter.h:541-737) ----
-struct Cell { int16_t mv[2][2]; int8_t dpb[2]; uint8_t flags; int8_t qp; uint8_t tuLog2; uint8_t pad[3]; };
-static_assert(sizeof(Cell) == 16, "havoc_mi355x_cell");
+using Cell = havoc_mi355x_cell;
 
 // LoopFilter.h:402-409
 __device__ __forceinline__ bool sameMotion1(const Cell &a, int la, const Cell &b, int lb)
 {
-    if (a.dpb[la] != b.dpb[lb]) return false;
-    if (a.dpb[la] < 0) return true;
+    if (a.dpb_index[la] != b.dpb_index[lb]) return false;
+    if (a.dpb_index[la] < 0) return true;
     return abs(a.mv[la][0] - b.mv[lb][0]) < 4 && abs(a.mv[la][1] - b.mv[lb][1]) < 4;
 }
 // LoopFilter.h:411-422
@@ -238,14 +238,14 @@ __device__ __forceinline__ bool sameMotion(const Cell &a, const Cell &b)
 __device__ __forceinline__ int edgeStrength(const Cell *a, const Cell *b, int pos, bool puEdge)
 {
     int bs = 0;
-    if (a && (pos & ((1 << a->tuLog2) - 1)) == 0)      // the right / bottom edge of a's transform block
+    if (a && (pos & ((1 << a->tu_log2) - 1)) == 0)      // the right / bottom edge of a's transform block
         bs = max(bs, (a->flags & HAVOC_CELL_INTRA) ? 2 : ((a->flags & HAVOC_CELL_CODED) ? 1 : 0));
-    if (b && (pos & ((1 << b->tuLog2) - 1)) == 0)      // the left / top edge of b's
+    if (b && (pos & ((1 << b->tu_log2) - 1)) == 0)      // the left / top edge of b's
         bs = max(bs, (b->flags & HAVOC_CELL_INTRA) ? 2 : ((b->flags & HAVOC_CELL_CODED) ? 1 : 0));
     if (b && puEdge && !(b->flags & HAVOC_CELL_INTRA))
     {
         Cell none;
-        none.dpb[0] = none.dpb[1] = -1;
+        none.dpb_index[0] = none.dpb_index[1] = -1;
         none.mv[0][0] = none.mv[0][1] = none.mv[1][0] = none.mv[1][1] = 0;
         if (!sameMotion(a ? *a : none, *b)) bs = max(bs, 1);
     }
@@ -279,16 +279,16 @@ __global__ __launch_bounds__(256) void k_derive_bs(const Cell *__restrict__ cell
         // available (LoopFilter.h:484-510): with one slice, the picture's left column and top row
         if (rx == 0) packed &= 0xF0;
         if (ry == 0) packed &= 0x0F;
-        if (const Cell *c = at(rx * 2, ry * 2)) d = (int8_t)((c->qp << 1) | ((c->flags & HAVOC_CELL_NO_FILTER) ? 1 : 0));
+        if (const Cell *c = at(rx * 2, ry * 2)) d = (int8_t)((c->qp_y << 1) | ((c->flags & HAVOC_CELL_NO_FILTER) ? 1 : 0));
     }
     data[i] = d;
     bsOut[i] = (uint8_t)packed;
 }
 
-hipError_t launch_derive_bs(hipStream_t st, const void *cells, long cstride, int width, int height, int8_t *data, uint8_t *bs)
+hipError_t launch_derive_bs(hipStream_t st, const Cell *cells, long cstride, int width, int height, int8_t *data, uint8_t *bs)
 {
     const int gridW = (width + 63) / 64 * 8 + 1, gridH = (height + 63) / 64 * 8 + 1;
-    hipLaunchKernelGGL(k_derive_bs, dim3((gridW * gridH + 255) / 256), dim3(256), 0, st, (const Cell *)cells, cstride, width, height, gridW, gridH, data, bs);
+    hipLaunchKernelGGL(k_derive_bs, dim3((gridW * gridH + 255) / 256), dim3(256), 0, st, cells, cstride, width, height, gridW, gridH, data, bs);
     return hipGetLastError();
 }
 

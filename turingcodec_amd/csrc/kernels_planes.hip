@@ -14,6 +14,7 @@
 // All phases use the two-pass formula with the {..,64,..} filter for a zero phase, which is bit-identical to the
 // reference's one-pass H-only / V-only forms for bit depths 8..10 (havoc/pred_inter.cpp:930-937 does the same).
 #include "common.h"
+#include "launch.h"
 #include "interp.h"
 
 namespace havoc_gpu {

@@ -15,6 +15,7 @@
 // chain afterwards: bit exact, but 8x the arithmetic on 85 % zero groups and an LDS footprint that left 3 workgroups per CU; it
 // took 1.9 ms per 1080p picture against 0.93 ms for the form below.  profiles/r02_experiments.md has the numbers.)
 #include "common.h"
+#include "launch.h"
 #include "rdoq_work.h"
 #include "cabac_tables.h"
 
@@ -59,8 +60,6 @@ namespace {
 
 typedef short s16x2v __attribute__((ext_vector_type(2)));
 typedef unsigned short u16x2v __attribute__((ext_vector_type(2)));
-
-static_assert(sizeof(havoc_mi355x_rdoq_job) == sizeof(RdoqJob), "rdoq job layout");
 
 // what a lane knows about its transform block
 struct Block
@@ -1474,11 +1473,10 @@ static hipError_t rdoq_order_and_walk(hipStream_t st, int bitDepth, int log2, in
     return hipGetLastError();
 }
 
-hipError_t launch_rdoq(hipStream_t st, int bitDepth, int log2, int16_t *dst, const int16_t *src, const uint8_t *states, const void *jobs, int njobs, int32_t *cbf,
+hipError_t launch_rdoq(hipStream_t st, int bitDepth, int log2, int16_t *dst, const int16_t *src, const uint8_t *states, const RdoqJob *j, int njobs, int32_t *cbf,
                        void *workspace)
 {
     if (njobs <= 0) return hipSuccess;
-    const RdoqJob *j = static_cast<const RdoqJob *>(jobs);
     RdoqWork *work = static_cast<RdoqWork *>(workspace);
     const int wgs = (njobs + 63) / 64;
     if (log2 <= 3)
@@ -1525,12 +1523,11 @@ hipError_t launch_rdoq(hipStream_t st, int bitDepth, int log2, int16_t *dst, con
 
 // Rdoq::runQuantisation for 16x16 / 32x32 blocks whose scan was done by havoc_mi355x_tu_forward_scan (RdoqInfo per block in the workspace, level
 // blocks zeroed): histogram from the 32-byte records, order, walk
-hipError_t launch_rdoq_prescanned(hipStream_t st, int bitDepth, int log2, int16_t *dst, const int16_t *src, const uint8_t *states, const void *jobs, int njobs,
+hipError_t launch_rdoq_prescanned(hipStream_t st, int bitDepth, int log2, int16_t *dst, const int16_t *src, const uint8_t *states, const RdoqJob *j, int njobs,
                                   int32_t *cbf, void *workspace)
 {
     if (njobs <= 0) return hipSuccess;
     if (log2 != 4 && log2 != 5) return hipErrorInvalidValue;
-    const RdoqJob *j = static_cast<const RdoqJob *>(jobs);
     RdoqWork *work = static_cast<RdoqWork *>(workspace);
     if (inJobOrder(log2, njobs)) return rdoq_order_and_walk(st, bitDepth, log2, dst, src, states, j, njobs, cbf, work, true);
     hipError_t e = hipMemsetAsync(work, 0, sizeof(RdoqWork), st);

@@ -15,14 +15,14 @@
 // the order WITHIN a context matters.  Sign bits are popcount(sig) - signHidden.  The `snake` word of coded-sub-block flags, greater1Ctx / lastGreater1Flag
 // carried from the previously visited sub-block, countdown1 / countdown2 as a count of flags and "a greater1 was seen" are the reference's, restated.
 #include "common.h"
+#include "launch.h"
 #include "cabac_tables.h"
 
 namespace havoc_gpu {
 
 namespace {
 
-struct RateJob { int32_t level_off, ctx_index, rate_index; uint8_t c_idx, scan_idx, sdh, count; int32_t reserved[4]; };
-static_assert(sizeof(RateJob) == 32 && sizeof(RateJob) == sizeof(havoc_mi355x_residual_rate_job), "residual rate job layout");
+using RateJob = havoc_mi355x_residual_rate_job;
 
 enum { kLastX = HAVOC_RDOQ_CTX_LAST_X, kLastY = HAVOC_RDOQ_CTX_LAST_Y, kCsbf = HAVOC_RDOQ_CTX_CSBF, kSig = HAVOC_RDOQ_CTX_SIG, kG1 = HAVOC_RDOQ_CTX_GREATER1,
        kG2 = HAVOC_RDOQ_CTX_GREATER2 };
@@ -261,10 +261,9 @@ __global__ __launch_bounds__(64) void k_residual_rate(const int16_t *__restrict_
 
 } // namespace
 
-hipError_t launch_residual_rate(hipStream_t st, int log2, const int16_t *levels, const uint8_t *states, const void *jobs, int njobs, int64_t *rates, uint8_t *statesOut)
+hipError_t launch_residual_rate(hipStream_t st, int log2, const int16_t *levels, const uint8_t *states, const RateJob *j, int njobs, int64_t *rates, uint8_t *statesOut)
 {
     if (njobs <= 0) return hipSuccess;
-    const RateJob *j = static_cast<const RateJob *>(jobs);
     const dim3 grid((njobs + 63) / 64), wg(64);
     if (log2 == 2) hipLaunchKernelGGL(k_residual_rate<2>, grid, wg, 0, st, levels, states, j, njobs, rates, statesOut);
     else if (log2 == 3) hipLaunchKernelGGL(k_residual_rate<3>, grid, wg, 0, st, levels, states, j, njobs, rates, statesOut);

@@ -16,25 +16,22 @@
 // the 3x3 neighbourhood through the cache; the 4 x 5 edge categories accumulate in registers (select on the category, wave
 // reduction at the end), the 32 bands in per-wavefront LDS counters; the sums fit 32 bits (62 x 62 samples x 16-bit differences).
 #include "common.h"
+#include "launch.h"
 
 namespace havoc_gpu {
 
 namespace {
 
-struct SaoStatsJob { int32_t src_off, rec_off, w, h; };
-struct SaoJob { int32_t dst_off, src_off, w, h, type, eo_class; int16_t offsets[32]; int32_t reserved[2]; };
-static_assert(sizeof(SaoStatsJob) == sizeof(havoc_mi355x_sao_stats_job) && sizeof(SaoJob) == sizeof(havoc_mi355x_sao_job) && sizeof(SaoJob) == 96, "sao job layout");
-
 __device__ __forceinline__ int sign3(int v) { return (v > 0) - (v < 0); }
 
 template <int S>
 __global__ __launch_bounds__(256) void k_sao_stats(const char *__restrict__ srcPlane, long strideSrc, const char *__restrict__ recPlane, long strideRec,
-                                                   const SaoStatsJob *__restrict__ jobs, int shift, long long *__restrict__ out)
+                                                   const havoc_mi355x_sao_stats_job *__restrict__ jobs, int shift, long long *__restrict__ out)
 {
     typedef typename Sample<S>::T T;
     __shared__ int acc[104];            // the block's totals
     __shared__ int band[4][64];         // per wavefront: sums [0..31], counts [32..63] (fewer lanes fighting over a counter)
-    const SaoStatsJob job = jobs[blockIdx.x];
+    const havoc_mi355x_sao_stats_job job = jobs[blockIdx.x];
     const T *src = reinterpret_cast<const T *>(srcPlane) + job.src_off, *rec = reinterpret_cast<const T *>(recPlane) + job.rec_off;
     const int tid = threadIdx.x, wave = tid >> 6, iw = job.w - 2, ih = job.h - 2;
     if (tid < 104) acc[tid] = 0;
@@ -110,17 +107,14 @@ __global__ __launch_bounds__(256) void k_sao_stats(const char *__restrict__ srcP
 // band_offset_chroma_stats (turing/EncSao.h:62-109): ONE band histogram over the interiors of the Cb and the Cr block of a CTU -- per band
 // the number of samples and the sum of original - reconstruction of both planes -- and the four-band window holding most samples.
 // job = offsets of the Cb / Cr blocks in the source and reconstruction chroma planes; out[65 * job]: E[32], count[32], band position.
-struct SaoChromaJob { int32_t src_u, src_v, rec_u, rec_v, w, h, reserved[2]; };
-static_assert(sizeof(SaoChromaJob) == sizeof(havoc_mi355x_sao_chroma_job), "sao chroma job layout");
-
 template <int S>
 __global__ __launch_bounds__(256) void k_sao_band_chroma(const char *__restrict__ srcPlane, long strideSrc, const char *__restrict__ recPlane, long strideRec,
-                                                         const SaoChromaJob *__restrict__ jobs, int shift, long long *__restrict__ out)
+                                                         const havoc_mi355x_sao_chroma_job *__restrict__ jobs, int shift, long long *__restrict__ out)
 {
     typedef typename Sample<S>::T T;
     __shared__ int band[4][64];         // per wavefront: sums [0..31], counts [32..63]
     __shared__ int total[64];
-    const SaoChromaJob job = jobs[blockIdx.x];
+    const havoc_mi355x_sao_chroma_job job = jobs[blockIdx.x];
     const int tid = threadIdx.x, wave = tid >> 6, iw = job.w - 2, ih = job.h - 2;
     band[wave][tid & 63] = 0;
     __syncthreads();
@@ -159,11 +153,11 @@ __global__ __launch_bounds__(256) void k_sao_band_chroma(const char *__restrict_
 
 template <int S>
 __global__ __launch_bounds__(256) void k_sao_filter(char *__restrict__ dstPlane, long strideDst, const char *__restrict__ srcPlane, long strideSrc,
-                                                    const SaoJob *__restrict__ jobs, int bitDepth)
+                                                    const havoc_mi355x_sao_job *__restrict__ jobs, int bitDepth)
 {
     typedef typename Sample<S>::T T;
-    __shared__ SaoJob job;
-    if (threadIdx.x < sizeof(SaoJob) / 4) reinterpret_cast<int *>(&job)[threadIdx.x] = reinterpret_cast<const int *>(jobs + blockIdx.x)[threadIdx.x];
+    __shared__ havoc_mi355x_sao_job job;
+    if (threadIdx.x < sizeof(havoc_mi355x_sao_job) / 4) reinterpret_cast<int *>(&job)[threadIdx.x] = reinterpret_cast<const int *>(jobs + blockIdx.x)[threadIdx.x];
     __syncthreads();
     T *dst = reinterpret_cast<T *>(dstPlane) + job.dst_off;
     const T *src = reinterpret_cast<const T *>(srcPlane) + job.src_off;
@@ -191,30 +185,27 @@ __global__ __launch_bounds__(256) void k_sao_filter(char *__restrict__ dstPlane,
 
 } // namespace
 
-hipError_t launch_sao_stats(hipStream_t st, int S, int bitDepth, const void *src, long strideSrc, const void *rec, long strideRec, const void *jobs, int njobs,
+hipError_t launch_sao_stats(hipStream_t st, int S, int bitDepth, const void *src, long strideSrc, const void *rec, long strideRec, const havoc_mi355x_sao_stats_job *j, int njobs,
                             int64_t *out)
 {
     if (njobs <= 0) return hipSuccess;
-    const SaoStatsJob *j = static_cast<const SaoStatsJob *>(jobs);
     if (S == 1) hipLaunchKernelGGL(k_sao_stats<1>, dim3(njobs), dim3(256), 0, st, (const char *)src, strideSrc, (const char *)rec, strideRec, j, bitDepth - 8, (long long *)out);
     else hipLaunchKernelGGL(k_sao_stats<2>, dim3(njobs), dim3(256), 0, st, (const char *)src, strideSrc, (const char *)rec, strideRec, j, bitDepth - 8, (long long *)out);
     return hipGetLastError();
 }
 
-hipError_t launch_sao_band_chroma(hipStream_t st, int S, int bitDepth, const void *src, long strideSrc, const void *rec, long strideRec, const void *jobs, int njobs,
+hipError_t launch_sao_band_chroma(hipStream_t st, int S, int bitDepth, const void *src, long strideSrc, const void *rec, long strideRec, const havoc_mi355x_sao_chroma_job *j, int njobs,
                                   int64_t *out)
 {
     if (njobs <= 0) return hipSuccess;
-    const SaoChromaJob *j = static_cast<const SaoChromaJob *>(jobs);
     if (S == 1) hipLaunchKernelGGL(k_sao_band_chroma<1>, dim3(njobs), dim3(256), 0, st, (const char *)src, strideSrc, (const char *)rec, strideRec, j, bitDepth - 8, (long long *)out);
     else hipLaunchKernelGGL(k_sao_band_chroma<2>, dim3(njobs), dim3(256), 0, st, (const char *)src, strideSrc, (const char *)rec, strideRec, j, bitDepth - 8, (long long *)out);
     return hipGetLastError();
 }
 
-hipError_t launch_sao_filter(hipStream_t st, int S, int bitDepth, void *dst, long strideDst, const void *src, long strideSrc, const void *jobs, int njobs)
+hipError_t launch_sao_filter(hipStream_t st, int S, int bitDepth, void *dst, long strideDst, const void *src, long strideSrc, const havoc_mi355x_sao_job *j, int njobs)
 {
     if (njobs <= 0) return hipSuccess;
-    const SaoJob *j = static_cast<const SaoJob *>(jobs);
     if (S == 1) hipLaunchKernelGGL(k_sao_filter<1>, dim3(njobs), dim3(256), 0, st, (char *)dst, strideDst, (const char *)src, strideSrc, j, bitDepth);
     else hipLaunchKernelGGL(k_sao_filter<2>, dim3(njobs), dim3(256), 0, st, (char *)dst, strideDst, (const char *)src, strideSrc, j, bitDepth);
     return hipGetLastError();

@@ -10,27 +10,20 @@
 // allows it, and its neighbours through L1 (row above and below, one sample either side, clamped into the picture: only samples the
 // reference restores ever see a clamped neighbour).  The restore decision is a predicate of the lane's position and the CTU's uniform
 // counters.  Nothing outside the picture is read or written.
+#include "launch.h"
 #include "sao_ctu.h"
-
-#include <cstddef>
 
 namespace havoc_gpu {
 
 namespace {
-
-struct SaoBounds { int32_t left, top, right, bottom, corners, reserved[3]; };
-struct SaoDecision { SaoComp comp[2]; int32_t merge_left, merge_up, dist, source; uint8_t ctx[4]; int32_t decided, reserved[4]; };
-static_assert(sizeof(SaoBounds) == sizeof(havoc_mi355x_sao_bounds) && sizeof(SaoBounds) == 32, "sao bounds layout");
-static_assert(sizeof(SaoDecision) == sizeof(havoc_mi355x_sao_decision) && offsetof(SaoDecision, decided) == offsetof(havoc_mi355x_sao_decision, decided),
-              "sao decision layout");
 
 struct SaoApplyArgs
 {
     const char *rec[3];
     char *dst[3];
     long rs[2], ds[2];                       // row strides in samples: [0] luma, [1] chroma
-    const SaoDecision *decisions;
-    const SaoBounds *bounds;                 // null: one slice, one tile
+    const havoc_mi355x_sao_decision *decisions;
+    const havoc_mi355x_sao_bounds *bounds;                 // null: one slice, one tile
     const int8_t *block_data;                // null: no disabled regions
     long block_stride;
     int width, height, log2, ctus_x, nctus, bd, flags;
@@ -83,10 +76,10 @@ __global__ __launch_bounds__(256) void k_sao_apply(const SaoApplyArgs a)
     __shared__ int16_t table[2][32];
     const int tid = threadIdx.x, ctu = xcd_block(blockIdx.x, gridDim.x);
     const int rx = ctu % a.ctus_x, ry = ctu / a.ctus_x, ctb = 1 << a.log2;
-    const SaoDecision &dec = a.decisions[ctu];
+    const havoc_mi355x_sao_decision &dec = a.decisions[ctu];
     sao_offset_table(table, dec.comp, tid, a.bd);
     // LoopFilter::Ctu of one slice and one tile when no bounds are given: only the picture's edges are unavailable
-    SaoBounds b;
+    havoc_mi355x_sao_bounds b;
     if (a.bounds)
         b = a.bounds[ctu];
     else
@@ -192,15 +185,15 @@ __global__ __launch_bounds__(256) void k_sao_apply(const SaoApplyArgs a)
 } // namespace
 
 hipError_t launch_sao_apply(hipStream_t st, int S, int bitDepth, int flags, int width, int height, int log2, const void *rec_y, const void *rec_cb,
-                            const void *rec_cr, long rsy, long rsc, void *dst_y, void *dst_cb, void *dst_cr, long dsy, long dsc, const void *decisions,
-                            const void *bounds, const int8_t *block_data, long block_stride)
+                            const void *rec_cr, long rsy, long rsc, void *dst_y, void *dst_cb, void *dst_cr, long dsy, long dsc, const havoc_mi355x_sao_decision *decisions,
+                            const havoc_mi355x_sao_bounds *bounds, const int8_t *block_data, long block_stride)
 {
     SaoApplyArgs a;
     a.rec[0] = static_cast<const char *>(rec_y), a.rec[1] = static_cast<const char *>(rec_cb), a.rec[2] = static_cast<const char *>(rec_cr);
     a.dst[0] = static_cast<char *>(dst_y), a.dst[1] = static_cast<char *>(dst_cb), a.dst[2] = static_cast<char *>(dst_cr);
     a.rs[0] = rsy, a.rs[1] = rsc, a.ds[0] = dsy, a.ds[1] = dsc;
-    a.decisions = static_cast<const SaoDecision *>(decisions);
-    a.bounds = static_cast<const SaoBounds *>(bounds);
+    a.decisions = decisions;
+    a.bounds = bounds;
     a.block_data = block_data;
     a.block_stride = block_stride;
     a.width = width, a.height = height, a.log2 = log2, a.bd = bitDepth, a.flags = flags;

@@ -12,6 +12,7 @@
 //
 // The double arithmetic must round where the reference's x86-64 build rounds: no fused multiply-add (`deltaD + lambda * rate` is
 // two roundings there), sums in the reference's order, divisions in double (v_div_scale/fmas/fixup: IEEE).
+#include "launch.h"
 #include "sao_ctu.h"
 
 #pragma clang fp contract(off)
@@ -20,9 +21,8 @@ namespace havoc_gpu {
 
 namespace {
 
-struct StatsJob { int32_t src_off, rec_off, w, h; };
-struct ChromaJob { int32_t src_u, src_v, rec_u, rec_v, w, h, reserved[2]; };
-static_assert(sizeof(StatsJob) == sizeof(havoc_mi355x_sao_stats_job) && sizeof(ChromaJob) == sizeof(havoc_mi355x_sao_chroma_job), "sao job layout");
+using StatsJob = havoc_mi355x_sao_stats_job;
+using ChromaJob = havoc_mi355x_sao_chroma_job;
 
 // the workspace: per CTU the statistics rows of kernels_sao.hip (Y 105, Cb 105, Cr 105, joint chroma bands 65 int64) and the jobs
 struct Work
@@ -254,16 +254,12 @@ __global__ __launch_bounds__(256) void k_sao_decide(const SaoCtu *__restrict__ c
 
 } // namespace
 
-hipError_t launch_sao_stats(hipStream_t, int S, int bd, const void *, long, const void *, long, const void *, int, int64_t *);
-hipError_t launch_sao_band_chroma(hipStream_t, int S, int bd, const void *, long, const void *, long, const void *, int, int64_t *);
-
 size_t sao_workspace_bytes(int nctus) { return nctus <= 0 ? 0 : (size_t)nctus * ((105 * 3 + 65) * 8 + 3 * sizeof(StatsJob) + sizeof(ChromaJob)); }
 
 hipError_t launch_sao_estimate(hipStream_t st, int S, int bd, double lambda, int flags, const void *srcY, const void *srcC, long ssy, long ssc, const void *recY,
-                               const void *recC, long rsy, long rsc, void *dstY, void *dstC, long dsy, long dsc, const void *ctus, int n, void *work, void *params)
+                               const void *recC, long rsy, long rsc, void *dstY, void *dstC, long dsy, long dsc, const SaoCtu *c, int n, void *work, SaoParams *p)
 {
     if (n <= 0) return hipSuccess;
-    const SaoCtu *c = static_cast<const SaoCtu *>(ctus);
     const Work wk = work_of(work, n);
     hipLaunchKernelGGL(k_sao_est_jobs, dim3((n + 255) / 256), dim3(256), 0, st, c, n, wk);
     hipError_t e;
@@ -271,7 +267,6 @@ hipError_t launch_sao_estimate(hipStream_t st, int S, int bd, double lambda, int
     if ((flags & 2) && ((e = launch_sao_stats(st, S, bd, srcC, ssc, recC, rsc, wk.jobC, 2 * n, (int64_t *)wk.statC)) != hipSuccess ||
                         (e = launch_sao_band_chroma(st, S, bd, srcC, ssc, recC, rsc, wk.jobB, n, (int64_t *)wk.bandC)) != hipSuccess))
         return e;
-    SaoParams *p = static_cast<SaoParams *>(params);
     if (S == 1)
         hipLaunchKernelGGL(k_sao_decide<1>, dim3(n), dim3(256), 0, st, c, wk, bd, lambda, flags, (const char *)srcY, (const char *)srcC, ssy, ssc, (const char *)recY,
                            (const char *)recC, rsy, rsc, (char *)dstY, (char *)dstC, dsy, dsc, p);

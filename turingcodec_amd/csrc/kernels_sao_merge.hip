@@ -16,14 +16,12 @@
 //   k_sao_merge_apply one workgroup per CTU: the decision record, and the CTU filtered again with its final parameters wherever they
 //                     differ from its estimate.
 #include "cabac_tables.h"
+#include "launch.h"
 #include "sao_ctu.h"
 
 namespace havoc_gpu {
 
 namespace {
-
-struct SaoDecision { SaoComp comp[2]; int32_t merge_left, merge_up, dist, source; uint8_t ctx[4]; int32_t decided, reserved[4]; };
-static_assert(sizeof(SaoDecision) == sizeof(havoc_mi355x_sao_decision) && sizeof(SaoDecision) == 128, "sao decision layout");
 
 constexpr int kMaxRow = 512;          // CTUs per row the decision pass holds in LDS (havoc_mi355x_sao_decide checks ctus_x against it)
 constexpr int kSpinLimit = 1 << 22;   // polls of a hand-off word before a wait gives up
@@ -347,7 +345,7 @@ __global__ __launch_bounds__(256) void k_sao_merge_rows(const SaoCtu *__restrict
 
 template <int S>
 __global__ __launch_bounds__(256) void k_sao_merge_apply(const SaoCtu *__restrict__ ctus, const SaoParams *__restrict__ params, MergeWork wk, int bd, Planes P,
-                                                         SaoDecision *__restrict__ out)
+                                                         havoc_mi355x_sao_decision *__restrict__ out)
 {
     typedef typename Sample<S>::T T;
     __shared__ SaoComp comp[2];
@@ -386,17 +384,14 @@ size_t sao_decide_workspace_bytes(int nctus) { return nctus <= 0 ? 0 : (size_t)n
 int sao_decide_max_row() { return kMaxRow; }
 
 hipError_t launch_sao_decide(hipStream_t st, int S, int bd, long long lambda, int flags, const void *srcY, const void *srcC, long ssy, long ssc, const void *recY,
-                             const void *recC, long rsy, long rsc, void *dstY, void *dstC, long dsy, long dsc, const void *ctus, int n, int cx, const void *params,
-                             int ctxMerge, int ctxType, void *work, void *out)
+                             const void *recC, long rsy, long rsc, void *dstY, void *dstC, long dsy, long dsc, const SaoCtu *c, int n, int cx, const SaoParams *p,
+                             int ctxMerge, int ctxType, void *work, havoc_mi355x_sao_decision *d)
 {
     if (n <= 0) return hipSuccess;
-    const SaoCtu *c = static_cast<const SaoCtu *>(ctus);
-    const SaoParams *p = static_cast<const SaoParams *>(params);
     const MergeWork wk = merge_work_of(work, n);
     const Planes P{ (const char *)srcY, (const char *)srcC, (const char *)recY, (const char *)recC, (char *)dstY, (char *)dstC, ssy, ssc, rsy, rsc, dsy, dsc };
     // rows by ticket: at most one workgroup per CU (cdna_hip_programming 1: the grid stays resident); without WPP the rows are a chain
     const int rows = n / cx, grid = (flags & 4) ? (rows < 256 ? rows : 256) : 1;
-    SaoDecision *d = static_cast<SaoDecision *>(out);
     if (S == 1)
     {
         hipLaunchKernelGGL(k_sao_merge_pre<1>, dim3(n), dim3(256), 0, st, c, p, cx, wk, bd, P);

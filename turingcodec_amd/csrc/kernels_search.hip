@@ -23,6 +23,7 @@
 // The source block (or the bi-directional "ideal" block), a window of the reference picture around the start candidates and the decided
 // vectors of the CTU and its neighbours live in LDS.  Exchange buffers alternate between two halves, so one barrier per exchange is enough.
 #include "common.h"
+#include "launch.h"
 
 #include "../search/search_abi.h"
 #include "../search/decision.hpp"

@@ -20,6 +20,7 @@
 // A launch is uniform in a size class (the reference's table is indexed by width class, havoc/pred_inter.h:47-50):
 // G = 8 / 32 / 128 / 256 lanes per PU for classes 8x8 / 16x16 / 32x32 / 64x64, 256 / G PUs per workgroup.
 #include "common.h"
+#include "launch.h"
 #include "interp.h"
 
 namespace havoc_gpu {
@@ -202,7 +203,7 @@ static hipError_t launch_subpel_satd_st(hipStream_t st, int bd, int maxw, int ma
 }
 
 hipError_t launch_subpel_satd(hipStream_t st, int S, int taps, int bd, int maxw, int maxh, const void *src, long ss, const void *ref, long rs,
-                              const void *jobs, int n, int32_t *cost)
+                              const havoc_mi355x_pred_uni_job *jobs, int n, int32_t *cost)
 {
     if (n <= 0) return hipSuccess;
     const char *s = (const char *)src, *r = (const char *)ref;

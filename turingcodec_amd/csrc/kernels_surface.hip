@@ -12,6 +12,7 @@
 // 16-bit samples: v_sad_u16 on dword pairs, odd offsets through v_alignbyte.
 // A job with a small surface (the 11x11 / 3x3 bi-prediction grids) shares its workgroup with other jobs.
 #include "common.h"
+#include "launch.h"
 
 namespace havoc_gpu {
 
@@ -208,7 +209,7 @@ __global__ __launch_bounds__(kSurfThreads) void k_sad_surface(const char *__rest
 
 template <int S, int NG>
 static hipError_t surface_launch(hipStream_t st, int range, int max_w, int max_h, const void *src, long ss, const void *ref, long sr,
-                                 const void *jobs, int n, int32_t *out)
+                                 const havoc_mi355x_surface_job *jobs, int n, int32_t *out)
 {
     SurfGeom g;
     g.R = range;
@@ -237,7 +238,7 @@ static hipError_t surface_launch(hipStream_t st, int range, int max_w, int max_h
 }
 
 hipError_t launch_sad_surface(hipStream_t st, int S, int range, int max_w, int max_h, const void *src, long ss, const void *ref, long sr,
-                              const void *jobs, int n, int32_t *out)
+                              const havoc_mi355x_surface_job *jobs, int n, int32_t *out)
 {
     if (n == 0) return hipSuccess;
     if (S == 2) return surface_launch<2, 2>(st, range, max_w, max_h, src, ss, ref, sr, jobs, n, out);

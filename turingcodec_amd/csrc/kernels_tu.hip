@@ -10,6 +10,7 @@
 // bank-conflict free.  Integer arithmetic throughout; the wrap (forward) / saturate (inverse) quirks of the reference
 // are reproduced exactly.
 #include "common.h"
+#include "launch.h"
 #include "transform_basis.h"
 
 namespace havoc_gpu {
@@ -241,7 +242,7 @@ static void go_fwd(hipStream_t st, int16_t *co, const int16_t *res, long sr, con
 }
 
 hipError_t launch_transform(hipStream_t st, int bitDepth, int log2, int trType, int16_t *coeffs, const int16_t *res, long stride_res,
-                            const void *jobs, int n)
+                            const havoc_mi355x_tu_job *jobs, int n)
 {
     if (n <= 0) return hipSuccess;
     const int32_t *j = (const int32_t *)jobs;
@@ -275,7 +276,7 @@ static void go_inv(hipStream_t st, int mode, char *dst, long sd, const char *pre
 
 // mode 0: int16 residual to resout; mode 1 / 2: add to 8-bit / 16-bit prediction
 hipError_t launch_inverse_transform(hipStream_t st, int mode, int bitDepth, int log2, int trType, void *dst, long sd, const void *pred, long sp,
-                                    int16_t *resout, const int16_t *coeffs, const void *jobs, int n)
+                                    int16_t *resout, const int16_t *coeffs, const havoc_mi355x_tu_job *jobs, int n)
 {
     if (n <= 0) return hipSuccess;
     const int32_t *j = (const int32_t *)jobs;
@@ -298,21 +299,21 @@ hipError_t launch_inverse_transform(hipStream_t st, int mode, int bitDepth, int 
     return hipGetLastError();
 }
 
-hipError_t launch_level_stats(hipStream_t st, const int16_t *levels, const void *jobs, int n, int32_t *out)
+hipError_t launch_level_stats(hipStream_t st, const int16_t *levels, const int32_t *jobs, int n, int32_t *out)
 {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_level_stats, dim3((n + 3) / 4), dim3(256), 0, st, levels, (const int32_t *)jobs, n, out);
+    hipLaunchKernelGGL(k_level_stats, dim3((n + 3) / 4), dim3(256), 0, st, levels, jobs, n, out);
     return hipGetLastError();
 }
 
-hipError_t launch_quantize(hipStream_t st, int16_t *dst, const int16_t *src, const void *jobs, int n, int32_t *cbf)
+hipError_t launch_quantize(hipStream_t st, int16_t *dst, const int16_t *src, const havoc_mi355x_quant_job *jobs, int n, int32_t *cbf)
 {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_quantize, dim3((n + 3) / 4), dim3(256), 0, st, dst, src, (const int32_t *)jobs, n, cbf);
     return hipGetLastError();
 }
 
-hipError_t launch_quantize_inverse(hipStream_t st, int16_t *dst, const int16_t *src, const void *jobs, int n)
+hipError_t launch_quantize_inverse(hipStream_t st, int16_t *dst, const int16_t *src, const havoc_mi355x_quant_job *jobs, int n)
 {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_quantize_inverse, dim3((n + 3) / 4), dim3(256), 0, st, dst, src, (const int32_t *)jobs, n);
@@ -320,7 +321,7 @@ hipError_t launch_quantize_inverse(hipStream_t st, int16_t *dst, const int16_t *
 }
 
 hipError_t launch_quantize_reconstruct(hipStream_t st, int log2, uint8_t *rec, long sr, const uint8_t *pred, long sp, const int16_t *res,
-                                       const void *jobs, int n)
+                                       const havoc_mi355x_tu_job *jobs, int n)
 {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_quantize_reconstruct, dim3((n + 3) / 4), dim3(256), 0, st, rec, sr, pred, sp, res, (const int32_t *)jobs, n, log2);
@@ -328,7 +329,7 @@ hipError_t launch_quantize_reconstruct(hipStream_t st, int log2, uint8_t *rec, l
 }
 
 hipError_t launch_residual(hipStream_t st, int S, int16_t *res, long sres, const int32_t *res_off, const void *src, long ss, const void *pred, long sp,
-                           const void *jobs, int n)
+                           const havoc_mi355x_pair_job *jobs, int n)
 {
     if (n <= 0) return hipSuccess;
     if (S == 1)

@@ -14,6 +14,7 @@
 
 #include <cstdlib>
 #include "transform_basis.h"
+#include "launch.h"
 #include "rdoq_work.h"
 
 namespace havoc_gpu {
@@ -346,7 +347,7 @@ __global__ __launch_bounds__(64) void k_intra_measure(int16_t *__restrict__ coef
 }
 
 hipError_t launch_intra_measure(hipStream_t st, int S, int bd, int log2, int16_t *coeffs, int16_t *coeffsDct, int32_t *satd, void *rec0, uint32_t *ssd0, const void *src,
-                                long ss, const void *pred, long sp, const void *jobs, int n, int withSatd)
+                                long ss, const void *pred, long sp, const havoc_mi355x_tu_fused_job *jobs, int n, int withSatd)
 {
     if (n <= 0) return hipSuccess;
     if (log2 < 2 || log2 > 5) return hipErrorInvalidValue;
@@ -550,14 +551,13 @@ static hipError_t launch_fwd_s(hipStream_t st, int bd, int log2, int tr, int16_t
 }
 
 // tu_forward with the RDOQ scan folded in (16x16 / 32x32 DCT blocks)
-hipError_t launch_tu_forward_scan(hipStream_t st, int S, int bd, int log2, int16_t *coeffs, const void *src, long ss, const void *pred, long sp, const void *jobs,
-                                  int n, const void *rdoq_jobs, int16_t *levels, void *workspace)
+hipError_t launch_tu_forward_scan(hipStream_t st, int S, int bd, int log2, int16_t *coeffs, const void *src, long ss, const void *pred, long sp,
+                                  const havoc_mi355x_tu_fused_job *jobs, int n, const RdoqJob *rj, int16_t *levels, void *workspace)
 {
     if (n <= 0) return hipSuccess;
     if (log2 != 4 && log2 != 5) return hipErrorInvalidValue;
     const char *s8 = (const char *)src, *p8 = (const char *)pred;
     const int32_t *j = (const int32_t *)jobs;
-    const RdoqJob *rj = (const RdoqJob *)rdoq_jobs;
     RdoqWork *w = (RdoqWork *)workspace;
     const int tpw = 64 >> log2;
     const dim3 g((n + tpw - 1) / tpw), b(64);
@@ -570,7 +570,7 @@ hipError_t launch_tu_forward_scan(hipStream_t st, int S, int bd, int log2, int16
 }
 
 hipError_t launch_tu_forward(hipStream_t st, int S, int bd, int log2, int tr, int16_t *coeffs, const void *src, long ss, const void *pred, long sp,
-                             const void *jobs, int n)
+                             const havoc_mi355x_tu_fused_job *jobs, int n)
 {
     if (n <= 0) return hipSuccess;
     return S == 1 ? launch_fwd_s<1>(st, bd, log2, tr, coeffs, (const char *)src, ss, (const char *)pred, sp, (const int32_t *)jobs, n)
@@ -608,7 +608,7 @@ static hipError_t launch_rec_s(hipStream_t st, int bd, int log2, int tr, int sca
 }
 
 hipError_t launch_tu_reconstruct(hipStream_t st, int S, int bd, int log2, int tr, int scale, int shift, void *rec, long sr, const void *pred, long sp,
-                                 const void *src, long ss, const int16_t *levels, const void *jobs, int n, uint32_t *ssd)
+                                 const void *src, long ss, const int16_t *levels, const havoc_mi355x_tu_fused_job *jobs, int n, uint32_t *ssd)
 {
     if (n <= 0) return hipSuccess;
     return S == 1 ? launch_rec_s<1>(st, bd, log2, tr, scale, shift, (char *)rec, sr, (const char *)pred, sp, (const char *)src, ss, levels,

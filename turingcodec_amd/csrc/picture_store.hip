@@ -13,10 +13,9 @@
 // any plane of a picture with one base pointer; the 16 fractional-sample luma planes of a reference picture
 // (havoc_mi355x_interp_planes) are made on first request and kept with the picture.
 #include "ctx.h"
+#include "launch.h"
 
 namespace havoc_gpu {
-hipError_t launch_pad_block(hipStream_t, int S, void *, long, int, int, long, int, int, int, int, int);
-hipError_t launch_interp_planes(hipStream_t, int S, int bd, void *, long, const void *, long, int, int, int, int);
 
 // dst plane (T samples) <- src rows of U samples, value << shift
 template <typename T, typename U>

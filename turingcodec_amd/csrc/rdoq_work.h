@@ -7,15 +7,11 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "../../include/havoc_mi355x.h"
+
 namespace havoc_gpu {
 
-struct RdoqJob   // == havoc_mi355x_rdoq_job
-{
-    int32_t dst_off, src_off, quant_scale, quant_shift, inv_scale, lambda_q16, sdh_factor, ctx_index;
-    uint8_t c_idx, scan_idx, is_intra, sdh;
-    int32_t reserved[3];
-};
-static_assert(sizeof(RdoqJob) == 48, "rdoq job layout");
+using RdoqJob = havoc_mi355x_rdoq_job;
 
 struct RdoqInfo { uint64_t mask, mask2, mask3; int64_t sumSq; };      // groups holding a rounded level > 0 / > 1 / > 2 (bit = raster group position), sum of squared coefficients
 constexpr int kBins = 66;                               // 0..64 groups to walk (+1 spare)

@@ -9,11 +9,9 @@ namespace havoc_gpu {
 
 namespace {
 
-struct SaoCtu { int32_t src_y, src_cb, src_cr, rec_y, rec_cb, rec_cr, dst_y, dst_cb, dst_cr, w, h, reserved, stat_src_cb, stat_src_cr, stat_rec_cb, stat_rec_cr; };
-struct SaoComp { int32_t type, eo_class, band_position, offset_abs[4], offset_sign[4]; };
-struct SaoParams { SaoComp comp[2]; int32_t dist_sao, dist_off; uint32_t ssd_sao[3], ssd_off[3]; int32_t reserved[2]; };
-static_assert(sizeof(SaoCtu) == sizeof(havoc_mi355x_sao_ctu) && sizeof(SaoCtu) == 64, "sao ctu layout");
-static_assert(sizeof(SaoParams) == sizeof(havoc_mi355x_sao_params) && sizeof(SaoParams) == 128, "sao params layout");
+using SaoCtu = havoc_mi355x_sao_ctu;
+using SaoComp = havoc_mi355x_sao_component;
+using SaoParams = havoc_mi355x_sao_params;
 
 // a CTU the kernels can measure: luma 8..64 even (chroma 4..32); any other record is reported off and left alone
 __device__ __forceinline__ bool ctu_ok(const SaoCtu &c) { return c.w >= 8 && c.h >= 8 && c.w <= 64 && c.h <= 64 && !(c.w & 1) && !(c.h & 1); }
