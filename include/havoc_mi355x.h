@@ -693,6 +693,44 @@ typedef struct {
 int havoc_mi355x_residual_rate(havoc_mi355x_ctx *ctx, int log2TrafoSize, const int16_t *d_levels, const uint8_t *d_states, const havoc_mi355x_residual_rate_job *d_jobs,
                                int njobs, int64_t *d_rate, uint8_t *d_states_out);
 
+/* ---- the CABAC rate of one refined intra candidate (csrc/kernels_residual_rate.hip: k_intra_rate) ----
+ * What searchIntraPartition measures for a challenger with EstimateRateLuma "since the partition began" (turing/Search.hpp:199, 242-246): Syntax<IntraPartition>
+ * (turing/SyntaxCtu.hpp:704-722) from the contexts the partition started with, luma only (turing/EstimateRate.h:114-119 nulls cbf_cb, cbf_cr, the chroma residuals and
+ * intra_chroma_pred_mode).  One job = one candidate = one transform block of the launch's size; in the syntax's order
+ *   - prev_intra_luma_pred_flag, one context (turing/Binarization.h:395-452): 1 when the mode is in candModeList;
+ *   - mpm_idx, truncated Rice with cMax 2, bypass: 1 bit for 0, 2 bits for 1 or 2 (:454-487) -- else rem_intra_luma_pred_mode, 5 bypass bits (:489-502);
+ *   - split_transform_flag = 0 (a candidate is one transform block), ctxInc = 5 - log2TrafoSize (:617-634), where transform_tree codes it (SyntaxCtu.hpp:330-337):
+ *     the caller says so per job (HAVOC_INTRA_RATE_SPLIT_FLAG_CODED; libhavoc_search.so: havoc_search_intra_rate_flags has the rule);
+ *   - cbf_luma, always coded for intra, ctxInc = trafoDepth == 0 ? 1 : 0 (:637-651), at HAVOC_RDOQ_CTX_CBF_LUMA of the 128-byte snapshot;
+ *   - when the block has a level: its residual_coding with c_idx 0, exactly the walk of havoc_mi355x_residual_rate.
+ * Context-coded bins cost the Q15 table entry shifted to Q16 and move their context, bypass bins 1 << 16.  prev_intra_luma_pred_flag and split_transform_flag are not
+ * in the 128-byte snapshot: d_syntax_states holds them, HAVOC_INTRA_SYNTAX_CTX_BYTES per snapshot, indexed by the same ctx_index: */
+enum {
+    HAVOC_INTRA_SYNTAX_CTX_PREV_INTRA_LUMA_PRED_FLAG = 0,   /* prev_intra_luma_pred_flag [1] */
+    HAVOC_INTRA_SYNTAX_CTX_SPLIT_TRANSFORM_FLAG = 1,        /* split_transform_flag [3], by ctxInc = 5 - log2TrafoSize */
+    HAVOC_INTRA_SYNTAX_CTX_BYTES = 4
+};
+enum {
+    HAVOC_INTRA_RATE_SPLIT_FLAG_CODED = 1,   /* split_transform_flag is coded (as 0) */
+    HAVOC_INTRA_RATE_DEPTH_NONZERO = 2       /* trafoDepth != 0: the blocks of an NxN unit */
+};
+typedef struct {
+    int32_t level_off;   /* the block's n*n contiguous int16 levels (raster, as havoc_mi355x_rdoq writes them); multiple of 4 */
+    int32_t ctx_index;   /* the snapshot of d_states (128 bytes) and of d_syntax_states (4 bytes) the candidate starts from */
+    int32_t rate_index;  /* the candidate's rate -> d_rate[rate_index] */
+    uint8_t scan_idx, sdh;   /* as in havoc_mi355x_residual_rate_job */
+    uint8_t mpm_idx;     /* 0..2: the first x with mode == candModeList[x]; 3: rem_intra_luma_pred_mode */
+    uint8_t flags;       /* HAVOC_INTRA_RATE_* */
+    int32_t reserved[4];
+} havoc_mi355x_intra_rate_job;   /* sizeof: 32 */
+/* A job with mpm_idx > 3, scan_idx > 2, scan_idx != 0 with log2TrafoSize > 3, or HAVOC_INTRA_RATE_SPLIT_FLAG_CODED with log2TrafoSize == 2 is not walked: no level
+ * is read, d_rate[rate_index] = -1 and its output snapshots are its input snapshots.  An all-zero block still pays its prefix and cbf_luma = 0 and moves only those
+ * contexts.  level_off, ctx_index and rate_index are trusted.  d_states and d_syntax_states are never written.  d_states_out: NULL, or njobs x 128 bytes;
+ * d_syntax_states_out: NULL, or njobs x 4 bytes: the snapshot as candidate j left it -- what a chain from partition to partition would carry on from the champion.
+ * d_levels and d_rate 8-byte aligned.  No allocation, no synchronisation, no workspace: capturable into a HIP graph. */
+int havoc_mi355x_intra_rate(havoc_mi355x_ctx *ctx, int log2TrafoSize, const int16_t *d_levels, const uint8_t *d_states, const uint8_t *d_syntax_states,
+                            const havoc_mi355x_intra_rate_job *d_jobs, int njobs, int64_t *d_rate, uint8_t *d_states_out, uint8_t *d_syntax_states_out);
+
 /* The same two steps with the scan of the coefficients done where they are produced (16x16 / 32x32 blocks; round 3):
  *   tu_forward_scan  = tu_forward + the first pass of the device RDOQ (which 4x4 groups hold a rounded level, the block's energy -> d_work;
  *                      the level block of d_rdoq_jobs[i].dst_off zeroed).  d_rdoq_jobs[i] describes the same block as d_jobs[i]
@@ -709,6 +747,7 @@ int havoc_mi355x_rdoq_prescanned(havoc_mi355x_ctx *ctx, int bitDepth, int log2Tr
  * Not reference primitives: the reference takes them inline in searchIntraPartition (turing/Search.hpp:40-255).  A batch client that
  * refines a picture's intra partitions (libhavoc_search.so: havoc_search_intra_device) chains
  *     intra_satd35 -> intra_order -> intra_expand -> intra -> tu_forward -> rdoq -> tu_reconstruct -> level_stats -> intra_decide -> tu_reconstruct
+ * (havoc_search_intra_device_rated: ... -> tu_reconstruct -> intra_rate_jobs -> intra_rate -> intra_decide_rated -> tu_reconstruct, the reference's CABAC bits as the rate)
  * so that neither the 35 costs per partition nor the job records per candidate cross the link. */
 #define HAVOC_MI355X_INTRA_MAX_ORDER 12
 typedef struct
@@ -741,8 +780,8 @@ int havoc_mi355x_intra_expand(havoc_mi355x_ctx *ctx, const havoc_mi355x_intra_se
                               havoc_mi355x_intra_job *d_intra_jobs, havoc_mi355x_tu_fused_job *d_tu_jobs, havoc_mi355x_rdoq_job *d_rdoq_jobs, int32_t *d_stat_jobs,
                               int32_t *d_owner);
 /* Search.hpp:143-255: the first candidate with the smallest   mode rate + (1 + (cbf ? 2 * nonzero + sum_abs : 0) << 16) + reciprocal_lambda_q16 * ssd.
- * The RATE here is a stand-in, not the reference's (the RESIDUAL term can now be the reference's: havoc_mi355x_residual_rate measures it on the device; the intra chain
- * does not use it yet, and the mode bits in their CABAC state stay unpriced): its RD stage charges every mode -- candModeList[0] included -- the bits EstimateRateLuma measures in the CABAC state of
+ * The RATE here is a stand-in, not the reference's (havoc_mi355x_intra_decide_rated below takes the reference's: havoc_mi355x_intra_rate measures them on the
+ * device): the reference's RD stage charges every mode -- candModeList[0] included -- the bits EstimateRateLuma measures in the CABAC state of
  * that moment (prev_intra_luma_pred_flag, mpm_idx / rem_intra_luma_pred_mode, the residual), where this uses the first stage's offsets (rate_a_minus_c is 0 rate for
  * candModeList[0]) and a count of levels.  The order of evaluation, the Q16 arithmetic and the strict comparison are the reference's (pinned with the encoder's own rates:
  * tests/test_trace_pin.py); a caller with an entropy coder supplies real rates through the host form (search/tu_decision.hpp: decideIntraRd with a rate functor);
@@ -750,6 +789,20 @@ int havoc_mi355x_intra_expand(havoc_mi355x_ctx *ctx, const havoc_mi355x_intra_se
 int havoc_mi355x_intra_decide(havoc_mi355x_ctx *ctx, const havoc_mi355x_intra_mpm *d_mpm, const int32_t *d_order, const int32_t *d_count, const int32_t *d_slot,
                               const int32_t *d_cbf, const uint32_t *d_ssd, const int32_t *d_stats, const havoc_mi355x_tu_fused_job *d_tu_jobs, int n, int log2TrafoSize,
                               int32_t reciprocal_lambda_q16, havoc_mi355x_intra_choice *d_out, havoc_mi355x_tu_fused_job *d_final);
+/* the records of havoc_mi355x_intra_rate for the candidates havoc_mi355x_intra_expand laid out, one lane per candidate slot: job c = slot c (d_slot[i] + k) with
+ * level_off = d_rdoq_jobs[c].dst_off, its ctx_index, scan_idx and sdh, rate_index = c, mpm_idx = the first x with d_order[..][k] == cand_mode_list[x] (3: none) and the
+ * launch's flags (HAVOC_INTRA_RATE_*: one size of one kind of unit per launch) */
+int havoc_mi355x_intra_rate_jobs(havoc_mi355x_ctx *ctx, const havoc_mi355x_intra_mpm *d_mpm, const int32_t *d_order, const int32_t *d_count, const int32_t *d_slot,
+                                 const havoc_mi355x_rdoq_job *d_rdoq_jobs, int n, int flags, havoc_mi355x_intra_rate_job *d_jobs);
+/* havoc_mi355x_intra_decide with the rate supplied: cost = d_rates[s] + reciprocal_lambda_q16 * ssd[s] for candidate slot s (havoc_mi355x_intra_rate: mode bits,
+ * split_transform_flag, cbf_luma and the residual in their CABAC state, in place of the first stage's offsets and the stand-in).  The reference measures a challenger's
+ * rate only when its distortion alone is below the champion's cost (Search.hpp:242-246); rates are never negative, so measuring every candidate and comparing whole
+ * costs with `<` in refinement order picks the same champion at the same cost.  The order of evaluation, the count == 0 guard, the final job records and the 40-byte
+ * results are havoc_mi355x_intra_decide's.  d_stats may be NULL: nonzero / sum_abs of the results are then 0. */
+int havoc_mi355x_intra_decide_rated(havoc_mi355x_ctx *ctx, const havoc_mi355x_intra_mpm *d_mpm, const int32_t *d_order, const int32_t *d_count, const int32_t *d_slot,
+                                    const int32_t *d_cbf, const uint32_t *d_ssd, const int32_t *d_stats, const int64_t *d_rates,
+                                    const havoc_mi355x_tu_fused_job *d_tu_jobs, int n, int log2TrafoSize, int32_t reciprocal_lambda_q16, havoc_mi355x_intra_choice *d_out,
+                                    havoc_mi355x_tu_fused_job *d_final);
 
 /* ---- the transform-tree decision of inter units and the picture's block structure on the device (round 4; csrc/kernels_decide.hip) ----
  * reconstructInter's choice between one transform block and four (turing/Reconstruct.cpp:1296-1428; turingcodec_amd/search/tu_decision.hpp: decideRqt) from the outcomes of a

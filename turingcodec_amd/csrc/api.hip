@@ -27,6 +27,8 @@ static_assert(offsetof(havoc_mi355x_sao_params, dist_sao) == 88 && offsetof(havo
 static_assert(sizeof(havoc_mi355x_sao_decision) == 128 && offsetof(havoc_mi355x_sao_decision, merge_left) == 88 &&
               offsetof(havoc_mi355x_sao_decision, ctx_merge_before) == 104 && offsetof(havoc_mi355x_sao_decision, decided) == 108, "sao record ABI");
 static_assert(sizeof(havoc_mi355x_residual_rate_job) == 32 && offsetof(havoc_mi355x_residual_rate_job, c_idx) == 12, "job ABI");
+static_assert(sizeof(havoc_mi355x_intra_rate_job) == 32 && offsetof(havoc_mi355x_intra_rate_job, scan_idx) == 12 && offsetof(havoc_mi355x_intra_rate_job, flags) == 15,
+              "job ABI");
 static_assert(sizeof(havoc_mi355x_intra_mpm) == 40 && sizeof(havoc_mi355x_intra_choice) == 40, "job ABI");
 static_assert(sizeof(havoc_mi355x_rdoq_job) == 48 && offsetof(havoc_mi355x_rdoq_job, c_idx) == 32, "job ABI");
 static_assert(sizeof(havoc_mi355x_sad4_run) == 32 && sizeof(havoc_mi355x_sao_stats_job) == 16 && sizeof(havoc_mi355x_sao_chroma_job) == 32 && sizeof(havoc_mi355x_sao_job) == 96, "job ABI");
@@ -825,8 +827,31 @@ int havoc_mi355x_intra_decide(havoc_mi355x_ctx *ctx, const havoc_mi355x_intra_mp
                               int32_t reciprocal_lambda_q16, havoc_mi355x_intra_choice *d_out, havoc_mi355x_tu_fused_job *d_final)
 {
     REQUIRE_CTX(); REQUIRE(n >= 0, "n < 0"); REQUIRE(log2TrafoSize >= 2 && log2TrafoSize <= 5, "log2TrafoSize must be 2..5");
-    return check(launch_intra_decide(LS(ctx), d_mpm, d_order, d_count, d_slot, d_cbf, d_ssd, d_stats, d_tu_jobs, n, log2TrafoSize, reciprocal_lambda_q16, d_out, d_final),
+    return check(launch_intra_decide(LS(ctx), d_mpm, d_order, d_count, d_slot, d_cbf, d_ssd, d_stats, d_tu_jobs, n, log2TrafoSize, reciprocal_lambda_q16, d_out, d_final,
+                                     nullptr),
                  "intra_decide");
+}
+
+int havoc_mi355x_intra_rate_jobs(havoc_mi355x_ctx *ctx, const havoc_mi355x_intra_mpm *d_mpm, const int32_t *d_order, const int32_t *d_count, const int32_t *d_slot,
+                                 const havoc_mi355x_rdoq_job *d_rdoq_jobs, int n, int flags, havoc_mi355x_intra_rate_job *d_jobs)
+{
+    REQUIRE_CTX(); REQUIRE(n >= 0, "n < 0"); REQUIRE(flags >= 0 && flags <= 3, "intra_rate_jobs: flags outside HAVOC_INTRA_RATE_*");
+    REQUIRE(n == 0 || (d_mpm && d_order && d_count && d_slot && d_rdoq_jobs && d_jobs), "intra_rate_jobs: null device pointer");
+    return check(launch_intra_rate_jobs(LS(ctx), d_mpm, d_order, d_count, d_slot, d_rdoq_jobs, n, flags, d_jobs), "intra_rate_jobs");
+}
+
+int havoc_mi355x_intra_decide_rated(havoc_mi355x_ctx *ctx, const havoc_mi355x_intra_mpm *d_mpm, const int32_t *d_order, const int32_t *d_count, const int32_t *d_slot,
+                                    const int32_t *d_cbf, const uint32_t *d_ssd, const int32_t *d_stats, const int64_t *d_rates,
+                                    const havoc_mi355x_tu_fused_job *d_tu_jobs, int n, int log2TrafoSize, int32_t reciprocal_lambda_q16, havoc_mi355x_intra_choice *d_out,
+                                    havoc_mi355x_tu_fused_job *d_final)
+{
+    REQUIRE_CTX(); REQUIRE(n >= 0, "n < 0"); REQUIRE(log2TrafoSize >= 2 && log2TrafoSize <= 5, "log2TrafoSize must be 2..5");
+    REQUIRE(d_rates != nullptr, "intra_decide_rated: null d_rates");
+    REQUIRE(n == 0 || (d_mpm && d_order && d_count && d_slot && d_cbf && d_ssd && d_tu_jobs && d_out && d_final), "intra_decide_rated: null device pointer");
+    REQUIRE((reinterpret_cast<uintptr_t>(d_rates) & 7) == 0, "intra_decide_rated: d_rates must be 8-byte aligned");
+    return check(launch_intra_decide(LS(ctx), d_mpm, d_order, d_count, d_slot, d_cbf, d_ssd, d_stats, d_tu_jobs, n, log2TrafoSize, reciprocal_lambda_q16, d_out, d_final,
+                                     d_rates),
+                 "intra_decide_rated");
 }
 
 int havoc_mi355x_quantize(havoc_mi355x_ctx *ctx, int16_t *d_dst, const int16_t *d_src, const havoc_mi355x_quant_job *d_jobs, int njobs, int32_t *d_cbf)
@@ -1008,6 +1033,17 @@ int havoc_mi355x_residual_rate(havoc_mi355x_ctx *ctx, int log2TrafoSize, const i
     REQUIRE((reinterpret_cast<uintptr_t>(d_levels) & 7) == 0 && (reinterpret_cast<uintptr_t>(d_rate) & 7) == 0, "residual_rate: d_levels and d_rate must be 8-byte aligned");
     REQUIRE(d_states_out != d_states, "residual_rate: d_states_out must not be d_states (which is never written)");
     return check(launch_residual_rate(LS(ctx), log2TrafoSize, d_levels, d_states, d_jobs, njobs, d_rate, d_states_out), "residual_rate");
+}
+
+int havoc_mi355x_intra_rate(havoc_mi355x_ctx *ctx, int log2TrafoSize, const int16_t *d_levels, const uint8_t *d_states, const uint8_t *d_syntax_states,
+                            const havoc_mi355x_intra_rate_job *d_jobs, int njobs, int64_t *d_rate, uint8_t *d_states_out, uint8_t *d_syntax_states_out)
+{
+    REQUIRE_CTX(); REQUIRE(log2TrafoSize >= 2 && log2TrafoSize <= 5, "log2TrafoSize must be 2..5"); REQUIRE(njobs >= 0, "njobs < 0");
+    REQUIRE(d_levels && d_states && d_syntax_states && d_jobs && d_rate, "intra_rate: null device pointer");
+    REQUIRE((reinterpret_cast<uintptr_t>(d_levels) & 7) == 0 && (reinterpret_cast<uintptr_t>(d_rate) & 7) == 0, "intra_rate: d_levels and d_rate must be 8-byte aligned");
+    REQUIRE(d_states_out != d_states, "intra_rate: d_states_out must not be d_states (which is never written)");
+    REQUIRE(d_syntax_states_out != d_syntax_states, "intra_rate: d_syntax_states_out must not be d_syntax_states (which is never written)");
+    return check(launch_intra_rate(LS(ctx), log2TrafoSize, d_levels, d_states, d_syntax_states, d_jobs, njobs, d_rate, d_states_out, d_syntax_states_out), "intra_rate");
 }
 
 } // extern "C"

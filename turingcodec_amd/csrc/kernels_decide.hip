@@ -11,7 +11,8 @@
 //                   matter to anything but addresses).
 //   k_intra_decide  a partition's candidates' outcomes -> the champion (decideIntraRd of search/tu_decision.hpp; Search.hpp:143-255: the first
 //                   candidate with the smallest mode rate + residual rate + ssd * reciprocal lambda) and the job that reconstructs it into the
-//                   caller's buffer.
+//                   caller's buffer.  RATED: the rate is the caller's per candidate (havoc_mi355x_intra_rate: the reference's CABAC bits; k_intra_rate_jobs
+//                   makes that kernel's records from the tables here).
 // The host forms of the same rules stay: they are what the per-call arms of the tests run over the reference's tables.
 #include "common.h"
 #include "launch.h"
@@ -112,10 +113,31 @@ __global__ __launch_bounds__(256) void k_intra_expand(const SearchJob *__restric
     owner[c] = i;
 }
 
+// every candidate slot -> its havoc_mi355x_intra_rate record: where k_intra_expand put its levels, which snapshot and scan its Rdoq job names, and where its mode
+// stands in candModeList (Binarization.h:432-447: the FIRST x with mode == candModeList[x]; none: rem_intra_luma_pred_mode)
+__global__ __launch_bounds__(256) void k_intra_rate_jobs(const IntraCtx *__restrict__ ictx, const int32_t *__restrict__ order, const int32_t *__restrict__ count,
+                                                         const int32_t *__restrict__ slot, const RdoqJob *__restrict__ rj, int n, int flags,
+                                                         havoc_mi355x_intra_rate_job *__restrict__ out)
+{
+    const long t = blockIdx.x * 256L + threadIdx.x;
+    const int i = (int)(t / kMaxOrder), k = (int)(t - (long)i * kMaxOrder);
+    if (i >= n || k >= count[i]) return;
+    const int mode = order[kMaxOrder * (long)i + k], c = slot[i] + k;
+    const IntraCtx m = ictx[i];
+    const RdoqJob r = rj[c];
+    const int mpm = mode == m.cand_mode_list[0] ? 0 : (mode == m.cand_mode_list[1] ? 1 : (mode == m.cand_mode_list[2] ? 2 : 3));
+    havoc_mi355x_intra_rate_job j = {r.dst_off, r.ctx_index, c, r.scan_idx, r.sdh, (uint8_t)mpm, (uint8_t)flags, {0, 0, 0, 0}};
+    out[c] = j;
+}
+
+// RATED: the whole rate of a candidate is the caller's (havoc_mi355x_intra_rate: the reference's bits) in place of the first stage's mode offsets and the stand-in;
+// nothing else differs.  The reference measures a challenger's rate only when its distortion alone is below the champion's cost (Search.hpp:242-246); rates are
+// never negative, so pricing every candidate and comparing whole costs with the strict `<` in refinement order picks the same champion at the same cost.
+template <bool RATED>
 __global__ __launch_bounds__(256) void k_intra_decide(const IntraCtx *__restrict__ ictx, const int32_t *__restrict__ order, const int32_t *__restrict__ count,
                                                       const int32_t *__restrict__ slot, const int32_t *__restrict__ cbf, const uint32_t *__restrict__ ssd,
-                                                      const int32_t *__restrict__ stats, const TuJob *__restrict__ tj, int n, int log2, int32_t reciprocalLambdaQ16,
-                                                      havoc_mi355x_intra_choice *__restrict__ out, TuJob *__restrict__ fin)
+                                                      const int32_t *__restrict__ stats, const int64_t *__restrict__ rates, const TuJob *__restrict__ tj, int n, int log2,
+                                                      int32_t reciprocalLambdaQ16, havoc_mi355x_intra_choice *__restrict__ out, TuJob *__restrict__ fin)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -125,9 +147,17 @@ __global__ __launch_bounds__(256) void k_intra_decide(const IntraCtx *__restrict
     for (int j = 0; j < count[i]; ++j)
     {
         const int mode = order[kMaxOrder * (long)i + j], s = base + j;
-        const int64_t modeRate = mode == c.cand_mode_list[0] ? c.rate_a_minus_c : ((mode == c.cand_mode_list[1] || mode == c.cand_mode_list[2]) ? c.rate_b_minus_c : 0);
-        const int64_t tuRate = (int64_t)(1 + (cbf[s] ? 2 * stats[2 * s] + stats[2 * s + 1] : 0)) << 16;      // search/tu_decision.hpp: tuRate (stand-in; havoc_mi355x_residual_rate has the reference's residual bits, not used here yet)
-        const int64_t cost = modeRate + tuRate + (int64_t)reciprocalLambdaQ16 * (int64_t)(int32_t)ssd[s];
+        const bool haveStats = !RATED || stats != nullptr;      // (no level statistics: the rated form)
+        const int nonzero = haveStats ? stats[2 * s] : 0, sumAbs = haveStats ? stats[2 * s + 1] : 0;
+        int64_t rate;
+        if (RATED)
+            rate = rates[s];
+        else
+        {
+            const int64_t modeRate = mode == c.cand_mode_list[0] ? c.rate_a_minus_c : ((mode == c.cand_mode_list[1] || mode == c.cand_mode_list[2]) ? c.rate_b_minus_c : 0);
+            rate = modeRate + ((int64_t)(1 + (cbf[s] ? 2 * nonzero + sumAbs : 0)) << 16);      // search/tu_decision.hpp: tuRate (stand-in; the RATED form has the reference's bits)
+        }
+        const int64_t cost = rate + (int64_t)reciprocalLambdaQ16 * (int64_t)(int32_t)ssd[s];
         ++r.evaluated;
         if (cost < r.cost)
         {
@@ -136,8 +166,8 @@ __global__ __launch_bounds__(256) void k_intra_decide(const IntraCtx *__restrict
             r.cost = cost;
             r.cbf = cbf[s];
             r.ssd = ssd[s];
-            r.nonzero = stats[2 * s];
-            r.sum_abs = stats[2 * s + 1];
+            r.nonzero = nonzero;
+            r.sum_abs = sumAbs;
         }
     }
     out[i] = r;
@@ -578,10 +608,25 @@ hipError_t launch_intra_expand(hipStream_t st, const SearchJob *parts, const int
 }
 
 hipError_t launch_intra_decide(hipStream_t st, const IntraCtx *ictx, const int32_t *order, const int32_t *count, const int32_t *slot, const int32_t *cbf, const uint32_t *ssd,
-                               const int32_t *stats, const TuJob *tj, int n, int log2, int32_t reciprocalLambdaQ16, havoc_mi355x_intra_choice *out, TuJob *fin)
+                               const int32_t *stats, const TuJob *tj, int n, int log2, int32_t reciprocalLambdaQ16, havoc_mi355x_intra_choice *out, TuJob *fin,
+                               const int64_t *rates)
 {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_intra_decide, dim3((n + 255) / 256), dim3(256), 0, st, ictx, order, count, slot, cbf, ssd, stats, tj, n, log2, reciprocalLambdaQ16, out, fin);
+    if (rates)
+        hipLaunchKernelGGL(k_intra_decide<true>, dim3((n + 255) / 256), dim3(256), 0, st, ictx, order, count, slot, cbf, ssd, stats, rates, tj, n, log2,
+                           reciprocalLambdaQ16, out, fin);
+    else
+        hipLaunchKernelGGL(k_intra_decide<false>, dim3((n + 255) / 256), dim3(256), 0, st, ictx, order, count, slot, cbf, ssd, stats, rates, tj, n, log2,
+                           reciprocalLambdaQ16, out, fin);
+    return hipGetLastError();
+}
+
+hipError_t launch_intra_rate_jobs(hipStream_t st, const IntraCtx *ictx, const int32_t *order, const int32_t *count, const int32_t *slot, const RdoqJob *rj, int n, int flags,
+                                  havoc_mi355x_intra_rate_job *out)
+{
+    if (n <= 0) return hipSuccess;
+    const long threads = (long)n * kMaxOrder;
+    hipLaunchKernelGGL(k_intra_rate_jobs, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, ictx, order, count, slot, rj, n, flags, out);
     return hipGetLastError();
 }
 

@@ -46,11 +46,15 @@ size_t rdoq_workspace_bytes(int njobs);
 hipError_t launch_rdoq(hipStream_t, int bd, int log2, int16_t *, const int16_t *, const uint8_t *, const havoc_mi355x_rdoq_job *, int, int32_t *, void *);
 hipError_t launch_rdoq_prescanned(hipStream_t, int bd, int log2, int16_t *, const int16_t *, const uint8_t *, const havoc_mi355x_rdoq_job *, int, int32_t *, void *);
 hipError_t launch_residual_rate(hipStream_t, int log2, const int16_t *, const uint8_t *, const havoc_mi355x_residual_rate_job *, int, int64_t *, uint8_t *);
+hipError_t launch_intra_rate(hipStream_t, int log2, const int16_t *, const uint8_t *, const uint8_t *, const havoc_mi355x_intra_rate_job *, int, int64_t *, uint8_t *, uint8_t *);
 hipError_t launch_intra_order(hipStream_t, const int32_t *, const havoc_mi355x_intra_mpm *, int, int32_t, int32_t *, int32_t *, int32_t *, int32_t *);
 hipError_t launch_intra_expand(hipStream_t, const havoc_mi355x_intra_search_job *, const int32_t *, const int32_t *, const int32_t *, const int32_t *, int, int, int, int, int,
                                int, int, int, havoc_mi355x_intra_job *, havoc_mi355x_tu_fused_job *, havoc_mi355x_rdoq_job *, int32_t *, int32_t *);
 hipError_t launch_intra_decide(hipStream_t, const havoc_mi355x_intra_mpm *, const int32_t *, const int32_t *, const int32_t *, const int32_t *, const uint32_t *,
-                               const int32_t *, const havoc_mi355x_tu_fused_job *, int, int, int32_t, havoc_mi355x_intra_choice *, havoc_mi355x_tu_fused_job *);
+                               const int32_t *, const havoc_mi355x_tu_fused_job *, int, int, int32_t, havoc_mi355x_intra_choice *, havoc_mi355x_tu_fused_job *,
+                               const int64_t *rates);
+hipError_t launch_intra_rate_jobs(hipStream_t, const havoc_mi355x_intra_mpm *, const int32_t *, const int32_t *, const int32_t *, const havoc_mi355x_rdoq_job *, int, int,
+                                  havoc_mi355x_intra_rate_job *);
 hipError_t launch_intra_fill_spare(hipStream_t, const int32_t *, int, int, havoc_mi355x_intra_job *, havoc_mi355x_tu_fused_job *, havoc_mi355x_rdoq_job *, int32_t *, int32_t *);
 hipError_t launch_intra_gather(hipStream_t, int S, const havoc_mi355x_intra_chain_layout *, const void *, const int32_t *, const uint8_t *,
                                const havoc_mi355x_intra_chain_part *, int, const havoc_mi355x_intra_search_job *, void *, havoc_mi355x_intra_mpm *);

@@ -97,6 +97,11 @@ def lib():
         L.havoc_search_intra_rd.restype = C.c_int
         L.havoc_search_intra_device.argtypes = [vp, C.c_int, C.c_int, vp, ip, vp, C.c_int, vp, vp, C.c_double, C.c_double, C.c_double, C.c_int, C.POINTER(RqtStats)]
         L.havoc_search_intra_device.restype = C.c_int
+        L.havoc_search_intra_device_rated.argtypes = [vp, C.c_int, C.c_int, vp, ip, vp, C.c_int, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_int,
+                                                      C.POINTER(RqtStats)]
+        L.havoc_search_intra_device_rated.restype = C.c_int
+        L.havoc_search_intra_rate_flags.argtypes = [C.c_int] * 5
+        L.havoc_search_intra_rate_flags.restype = C.c_int
         L.havoc_search_intra_modes.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, ip, vp, vp, C.c_int, vp, C.c_double, vp, vp]
         L.havoc_search_intra_modes.restype = C.c_int
         L.havoc_search_intra_chain.argtypes = [vp, C.c_int, C.c_int, vp, vp, ip, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_double, C.c_double, C.c_double, C.c_int, vp]
@@ -208,10 +213,27 @@ def _address(p):
     return int(p.value or 0) if isinstance(p, C.c_void_p) else int(p)
 
 
-def intra_device(ctx, S, bit_depth, d_src, src_stride, groups, d_states, quant, reciprocal_sqrt_lambda, lam, reciprocal_lambda, sdh=1):
+SEARCH_ENOTAVAILABLE = -200      # HAVOC_SEARCH_ENOTAVAILABLE
+
+
+def intra_rate_flags(log2, intra_split, max_transform_hierarchy_depth_intra=1, min_tb_log2=2, max_tb_log2=5):
+    """havoc_search_intra_rate_flags: the INTRA_RATE_* bits of an intra partition's transform block -- whether transform_tree codes split_transform_flag for it, and
+    whether its trafoDepth is non-zero (intra_split: one of the four partitions of an NxN unit).  The defaults are the reference encoder's set-up."""
+    return lib().havoc_search_intra_rate_flags(int(log2), int(bool(intra_split)), int(max_transform_hierarchy_depth_intra), int(min_tb_log2), int(max_tb_log2))
+
+
+def intra_device(ctx, S, bit_depth, d_src, src_stride, groups, d_states, quant, reciprocal_sqrt_lambda, lam, reciprocal_lambda, sdh=1, rates="stand-in",
+                 d_syntax_states=None):
     """havoc_search_intra_device: both stages of the intra partitions of all sizes, the decisions between the launches taken on the device.
     groups: dicts(log2, n, d_nb, d_jobs, d_ictx, d_ctu, d_rec) of device addresses; quant: int32 [4, 4] (rqt_quant).
-    Returns ({log2: INTRA_RD_RESULT_DT[n]}, stats)"""
+    rates="cabac" (havoc_search_intra_device_rated): every candidate is priced with the bits the reference's EstimateRateLuma measures for it -- mode bits,
+    split_transform_flag, cbf_luma, residual_coding, from the partition's snapshot -- instead of the stand-in.  d_syntax_states: 4 bytes per snapshot of d_states
+    (prev_intra_luma_pred_flag, split_transform_flag[0..2]); a group may carry "flags" (INTRA_RATE_*; default: a 2Nx2N partition, except 4x4: one of an NxN unit,
+    in the reference encoder's set-up).  Returns ({log2: INTRA_RD_RESULT_DT[n]}, stats)"""
+    if rates not in ("stand-in", "cabac"):
+        raise ValueError(f"rates must be 'stand-in' or 'cabac', not {rates!r}")
+    if (rates == "cabac") != (d_syntax_states is not None):
+        raise ValueError("d_syntax_states goes with rates='cabac', and only with it")
     table = np.zeros(len(groups), INTRA_GROUP_DT)
     outs = {}
     for row, g in zip(table, groups):
@@ -223,6 +245,17 @@ def intra_device(ctx, S, bit_depth, d_src, src_stride, groups, d_states, quant, 
         row["out"] = out.ctypes.data
     quant = np.ascontiguousarray(quant, np.int32)
     stats = RqtStats()
+    if rates == "cabac":
+        flags = np.array([g["flags"] if "flags" in g else intra_rate_flags(g["log2"], g["log2"] == 2) for g in groups], np.int32)
+        rc = lib().havoc_search_intra_device_rated(ctx, S, bit_depth, d_src, src_stride, table.ctypes.data, len(table), d_states, _address(d_syntax_states),
+                                                   flags.ctypes.data, quant.ctypes.data, float(reciprocal_sqrt_lambda), float(lam), float(reciprocal_lambda), int(sdh),
+                                                   C.byref(stats))
+        if rc == SEARCH_ENOTAVAILABLE:
+            raise RuntimeError("havoc_search_intra_device_rated: the device library has no havoc_mi355x_intra_rate / _intra_rate_jobs / _intra_decide_rated "
+                               "(there is no fallback to the stand-in rate)")
+        if rc != 0:
+            raise RuntimeError(f"havoc_search_intra_device_rated failed ({rc})")
+        return outs, stats
     rc = lib().havoc_search_intra_device(ctx, S, bit_depth, d_src, src_stride, table.ctypes.data, len(table), d_states, quant.ctypes.data, float(reciprocal_sqrt_lambda),
                                          float(lam), float(reciprocal_lambda), int(sdh), C.byref(stats))
     if rc != 0:

@@ -128,6 +128,9 @@ def _load():
         "tu_forward_scan": [_vp, _i, _i, _i, _vp, _vp, _ip, _vp, _ip, _vp, _i, _vp, _vp, _vp, C.c_size_t],
         "rdoq_prescanned": [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, C.c_size_t],
         "residual_rate": [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp],
+        "intra_rate": [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp],
+        "intra_rate_jobs": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
+        "intra_decide_rated": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_int32, _vp, _vp],
         "rqt_decide_rated": [_vp, _vp, _i, _vp, _vp, _vp, _vp, C.c_int64, C.c_ssize_t, _i, _i, _vp],
         "sao_stats": [_vp, _i, _i, _vp, _ip, _vp, _ip, _vp, _i, _vp],
         "sao_filter": [_vp, _i, _i, _vp, _ip, _vp, _ip, _vp, _i],
@@ -291,6 +294,13 @@ assert RDOQ_JOB_DT.itemsize == 48
 RESIDUAL_RATE_JOB_DT = np.dtype([("level_off", "<i4"), ("ctx_index", "<i4"), ("rate_index", "<i4"), ("c_idx", "u1"), ("scan_idx", "u1"), ("sdh", "u1"), ("count", "u1"),
                                  ("reserved", "<i4", 4)])
 assert RESIDUAL_RATE_JOB_DT.itemsize == 32
+
+# one havoc_mi355x_intra_rate_job (include/havoc_mi355x.h), 32 bytes; mpm_idx 3 = rem_intra_luma_pred_mode; flags: INTRA_RATE_*
+INTRA_RATE_JOB_DT = np.dtype([("level_off", "<i4"), ("ctx_index", "<i4"), ("rate_index", "<i4"), ("scan_idx", "u1"), ("sdh", "u1"), ("mpm_idx", "u1"), ("flags", "u1"),
+                              ("reserved", "<i4", 4)])
+assert INTRA_RATE_JOB_DT.itemsize == 32
+INTRA_RATE_SPLIT_FLAG_CODED, INTRA_RATE_DEPTH_NONZERO = 1, 2
+INTRA_SYNTAX_CTX_BYTES = 4      # HAVOC_INTRA_SYNTAX_CTX_*: prev_intra_luma_pred_flag, split_transform_flag[0..2]
 
 
 def rdoq_lambda(lam, inv_scale):
@@ -872,6 +882,37 @@ class Havoc:
             after = self.torch.zeros(max(len(jobs), 1) * 128, dtype=self.torch.uint8, device=self.device)
         self.residual_rate_d(log2, self.up(np.ascontiguousarray(levels, np.int16)), st, j, rates, after)
         return self.down(rates, np.int64)[:nr], self.down(after, np.uint8)[:len(jobs) * 128].reshape(-1, 128)
+
+    def intra_rate_d(self, log2, levels, states, syntax_states, jobs, rates, states_out=None, syntax_states_out=None):
+        """the CABAC rate of an intra candidate: mode bits, split_transform_flag, cbf_luma, residual_coding (havoc_mi355x_intra_rate); jobs: uint8 tensor holding
+        INTRA_RATE_JOB_DT records; syntax_states: uint8 tensor, 4 bytes per snapshot; rates: int64 tensor; the two outputs: None, or 128 / 4 bytes per job.  No sync."""
+        self._ck(self.L.havoc_mi355x_intra_rate(self.h, log2, _ptr(levels), _ptr(states), _ptr(syntax_states), _ptr(jobs), jobs.numel() // INTRA_RATE_JOB_DT.itemsize,
+                                                _ptr(rates), _ptr(states_out), _ptr(syntax_states_out)))
+
+    def intra_rate(self, log2, levels, states, syntax_states, jobs):
+        """numpy level: levels int16 (all blocks), states uint8 [k, 128], syntax_states uint8 [k, 4], jobs INTRA_RATE_JOB_DT array -> (rates int64 [max rate_index + 1],
+        the entries no job writes 0; states_after uint8 [njobs, 128]; syntax_states_after uint8 [njobs, 4])"""
+        jobs = np.ascontiguousarray(jobs, INTRA_RATE_JOB_DT)
+        nr = int(jobs["rate_index"].max()) + 1 if len(jobs) else 0
+        with self.torch.cuda.stream(self.tstream):
+            st = self.torch.from_numpy(np.ascontiguousarray(states, np.uint8).reshape(-1)).to(self.device)
+            sy = self.torch.from_numpy(np.ascontiguousarray(syntax_states, np.uint8).reshape(-1)).to(self.device)
+            j = self.torch.from_numpy(jobs.view(np.uint8).reshape(-1).copy()).to(self.device)
+            rates = self.torch.zeros(max(nr, 1), dtype=self.torch.int64, device=self.device)
+            after = self.torch.zeros(max(len(jobs), 1) * 128, dtype=self.torch.uint8, device=self.device)
+            after_sy = self.torch.zeros(max(len(jobs), 1) * INTRA_SYNTAX_CTX_BYTES, dtype=self.torch.uint8, device=self.device)
+        self.intra_rate_d(log2, self.up(np.ascontiguousarray(levels, np.int16)), st, sy, j, rates, after, after_sy)
+        return (self.down(rates, np.int64)[:nr], self.down(after, np.uint8)[:len(jobs) * 128].reshape(-1, 128),
+                self.down(after_sy, np.uint8)[:len(jobs) * INTRA_SYNTAX_CTX_BYTES].reshape(-1, INTRA_SYNTAX_CTX_BYTES))
+
+    def intra_rate_jobs_d(self, mpm, order, count, slot, rdoq_jobs, n, flags, jobs):
+        """INTRA_RATE_JOB_DT records of the candidates intra_expand laid out (havoc_mi355x_intra_rate_jobs): job c = candidate slot c; jobs: uint8 tensor.  No sync."""
+        self._ck(self.L.havoc_mi355x_intra_rate_jobs(self.h, _ptr(mpm), _ptr(order), _ptr(count), _ptr(slot), _ptr(rdoq_jobs), n, flags, _ptr(jobs)))
+
+    def intra_decide_rated_d(self, mpm, order, count, slot, cbf, ssd, stats, rates, tu_jobs, n, log2, rl_q16, out, final):
+        """havoc_mi355x_intra_decide_rated: the champion of every partition by rates[s] + rl_q16 * ssd[s]; stats may be None.  No sync."""
+        self._ck(self.L.havoc_mi355x_intra_decide_rated(self.h, _ptr(mpm), _ptr(order), _ptr(count), _ptr(slot), _ptr(cbf), _ptr(ssd), _ptr(stats), _ptr(rates),
+                                                        _ptr(tu_jobs), n, log2, rl_q16, _ptr(out), _ptr(final)))
 
     def ssd_linear_d(self, a, b, n, out):
         self._ck(self.L.havoc_mi355x_ssd_linear(self.h, _ptr(a), _ptr(b), n, _ptr(out)))

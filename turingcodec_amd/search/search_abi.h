@@ -113,6 +113,9 @@ typedef struct
 /* havoc_search_intra_chain: a level's mode-order step raised a flag (havoc_mi355x_intra_order's d_total[1]): returns HAVOC_SEARCH_EORDER - flags, i.e. -101 = an order
  * was cut at HAVOC_MI355X_INTRA_MAX_ORDER, -102 = a record was out of range, -103 = both; no result is written */
 #define HAVOC_SEARCH_EORDER (-100)
+/* havoc_search_intra_device_rated: the device library this one is bound to has not got havoc_mi355x_intra_rate_jobs / _intra_rate / _intra_decide_rated (they are looked
+ * up at first use, so that a device library without them still serves every other client) */
+#define HAVOC_SEARCH_ENOTAVAILABLE (-200)
 
 /* 35-mode intra stage: per partition */
 typedef struct

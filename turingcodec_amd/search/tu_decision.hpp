@@ -11,8 +11,10 @@
 // STAND-IN with the same inputs' summary (coded flag, number and magnitude of the levels), the same in every arm of the tests; it is what the
 // host clients of this header and havoc_mi355x_rqt_decide use.  The RESIDUAL part of the term can now be the reference's: havoc_mi355x_residual_rate
 // measures residual_coding's CABAC bits per transform block on the device, bit for bit, and havoc_mi355x_rqt_decide_rated takes them in place of
-// `tuRate` (DecisionPicture(residual_rates=True)).  Still not priced anywhere: cbf_luma, split_transform_flag, the chroma residuals of the tree,
-// and the intra mode bits in their CABAC state.  What is restated here -- and checked against the reference's tables + Rdoq.cpp -- is the
+// `tuRate` (DecisionPicture(residual_rates=True)).  An INTRA candidate's whole rate can be the reference's too: havoc_mi355x_intra_rate measures what
+// EstimateRateLuma measures for it -- the mode bits in their CABAC state, split_transform_flag, cbf_luma, the residual -- and havoc_mi355x_intra_decide_rated /
+// havoc_search_intra_device_rated decide by it.  Still not priced for the inter tree: cbf_luma, split_transform_flag and its chroma residuals.
+// What is restated here -- and checked against the reference's tables + Rdoq.cpp -- is the
 // order of evaluation, the uncoded short-cut, the cost arithmetic (Q16) and the strict comparison.
 #pragma once
 
@@ -71,7 +73,7 @@ havoc_rqt_result decideRqt(View &view, const havoc_rqt_cu &cu, Lambda reciprocal
 // inverse transform + add, SSD (reconstructIntraLuma -> Reconstruct.cpp:230-353) -- and the champion is the first candidate with the smallest
 // rate + ssd * reciprocalLambda (`challenger->cost2() < champion->cost2()`, strict; the reference adds a challenger's mode rate only when it is
 // already ahead on distortion, which cannot change who wins).  Rates: the mode's (relative to a non-MPM mode, as the first stage has them)
-// and the stand-in `tuRate` for the residual.
+// and the stand-in `tuRate` for the residual -- or, through the rate functor, a measured rate per candidate (the device form: havoc_mi355x_intra_decide_rated).
 // View: havoc_tu_outcome evaluate(int mode, int index).
 inline int intraScanIdx(int log2TrafoSize, int mode)      // Global.h:1212-1227, luma
 {

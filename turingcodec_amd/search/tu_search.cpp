@@ -10,6 +10,8 @@
 #include "batch_common.hpp"
 #include "tu_decision.hpp"
 
+#include <dlfcn.h>
+
 using namespace havoc_search;
 
 namespace {
@@ -24,6 +26,39 @@ struct LookupView
     havoc_tu_outcome evaluate(int, int, int, int depth) { return depth ? one[k++ & 3] : *zero; }
     int k = 0;
 };
+
+// The three entry points havoc_search_intra_device_rated needs, looked up at first use in the device library this one is bound to (the library that defines
+// havoc_mi355x_intra_decide): a stand-in device without them still loads this library with every symbol bound at once, and only the rated client reports
+// HAVOC_SEARCH_ENOTAVAILABLE.
+struct RatedApi
+{
+    decltype(&havoc_mi355x_intra_rate_jobs) rateJobs = nullptr;
+    decltype(&havoc_mi355x_intra_rate) rate = nullptr;
+    decltype(&havoc_mi355x_intra_decide_rated) decideRated = nullptr;
+    bool complete() const { return rateJobs && rate && decideRated; }
+};
+
+const RatedApi &ratedApi()
+{
+    static const RatedApi api = [] {
+        RatedApi a;
+        Dl_info info;
+        void *lib = nullptr;
+        if (dladdr(reinterpret_cast<void *>(&havoc_mi355x_intra_decide), &info) && info.dli_fname) lib = dlopen(info.dli_fname, RTLD_NOW | RTLD_NOLOAD);
+        void *from = lib ? lib : RTLD_DEFAULT;
+        a.rateJobs = reinterpret_cast<decltype(a.rateJobs)>(dlsym(from, "havoc_mi355x_intra_rate_jobs"));
+        a.rate = reinterpret_cast<decltype(a.rate)>(dlsym(from, "havoc_mi355x_intra_rate"));
+        a.decideRated = reinterpret_cast<decltype(a.decideRated)>(dlsym(from, "havoc_mi355x_intra_decide_rated"));
+        return a;      // (the handle stays open: the device library is in use for as long as this one is)
+    }();
+    return api;
+}
+
+// havoc_search_intra_device and havoc_search_intra_device_rated: one body.  api == nullptr: the stand-in rate (level_stats -> intra_decide); else the reference's
+// bits (intra_rate_jobs -> intra_rate -> intra_decide_rated) from d_syntax_states and the per-size flags.
+int intraDevice(havoc_mi355x_ctx *ctx, int S, int bitDepth, const void *d_src, intptr_t src_stride, const havoc_intra_group *groups, int ngroups, const uint8_t *d_states,
+                const havoc_rqt_quant quant[4], double reciprocal_sqrt_lambda, double lambda, double reciprocal_lambda, int sdh, havoc_rqt_stats *stats, const RatedApi *api,
+                const uint8_t *d_syntax_states, const int32_t *flags);
 
 } // namespace
 
@@ -383,6 +418,48 @@ int havoc_search_intra_device(havoc_mi355x_ctx *ctx, int S, int bitDepth, const 
                               const uint8_t *d_states, const havoc_rqt_quant quant[4], double reciprocal_sqrt_lambda, double lambda, double reciprocal_lambda, int sdh,
                               havoc_rqt_stats *stats)
 {
+    return intraDevice(ctx, S, bitDepth, d_src, src_stride, groups, ngroups, d_states, quant, reciprocal_sqrt_lambda, lambda, reciprocal_lambda, sdh, stats, nullptr, nullptr,
+                       nullptr);
+}
+
+// The same with the rate the reference measures for a challenger (EstimateRateLuma over Syntax<IntraPartition>, Search.hpp:242-246) in place of the stand-in:
+//   per size:  intra_expand -> intra -> tu_forward -> rdoq -> tu_reconstruct -> intra_rate_jobs -> intra_rate -> intra_decide_rated -> tu_reconstruct (champions)
+// (no level_stats: nonzero / sum_abs of the results are 0).  d_syntax_states: 4 bytes per snapshot of d_states (HAVOC_INTRA_SYNTAX_CTX_*); flags[g]: the
+// HAVOC_INTRA_RATE_* bits of group g's partitions (havoc_search_intra_rate_flags).  Every partition is priced from its own snapshot: carrying the champion's
+// contexts on from partition to partition is havoc_search_intra_chain's business, not done here.  HAVOC_SEARCH_ENOTAVAILABLE: the device library has not got
+// havoc_mi355x_intra_rate_jobs / _intra_rate / _intra_decide_rated.
+int havoc_search_intra_device_rated(havoc_mi355x_ctx *ctx, int S, int bitDepth, const void *d_src, intptr_t src_stride, const havoc_intra_group *groups, int ngroups,
+                                    const uint8_t *d_states, const uint8_t *d_syntax_states, const int32_t *flags, const havoc_rqt_quant quant[4],
+                                    double reciprocal_sqrt_lambda, double lambda, double reciprocal_lambda, int sdh, havoc_rqt_stats *stats)
+{
+    const RatedApi &api = ratedApi();
+    if (!api.complete()) return HAVOC_SEARCH_ENOTAVAILABLE;
+    if (!d_syntax_states || !flags) return HAVOC_MI355X_EINVAL;
+    for (int g = 0; g < ngroups && g < 16; ++g)
+        if (flags[g] < 0 || flags[g] > 3 || (groups && groups[g].log2 == 2 && (flags[g] & HAVOC_INTRA_RATE_SPLIT_FLAG_CODED))) return HAVOC_MI355X_EINVAL;
+    return intraDevice(ctx, S, bitDepth, d_src, src_stride, groups, ngroups, d_states, quant, reciprocal_sqrt_lambda, lambda, reciprocal_lambda, sdh, stats, &api,
+                       d_syntax_states, flags);
+}
+
+// transform_tree's condition for coding split_transform_flag (SyntaxCtu.hpp:330-337) and cbf_luma's ctxInc (Binarization.h:647) for the ONE transform block of an
+// intra partition (Syntax<IntraPartition>, SyntaxCtu.hpp:714-720: trafoDepth = IntraSplitFlag, MaxTrafoDepth = max_transform_hierarchy_depth_intra + IntraSplitFlag):
+// log2TrafoSize = the partition's size; intra_split = 1 for the four partitions of an NxN unit.  The reference encoder: depth 1, MinTbLog2SizeY 2,
+// MaxTbLog2SizeY min(5, CtbLog2SizeY) (Encoder.cpp:662-665) -- 2Nx2N partitions of 8, 16 and 32 code the flag, the 4x4 partitions of an NxN unit do not.
+int havoc_search_intra_rate_flags(int log2TrafoSize, int intra_split, int max_transform_hierarchy_depth_intra, int min_tb_log2_size, int max_tb_log2_size)
+{
+    const int trafoDepth = intra_split ? 1 : 0, maxTrafoDepth = max_transform_hierarchy_depth_intra + trafoDepth;
+    const bool coded = log2TrafoSize <= max_tb_log2_size && log2TrafoSize > min_tb_log2_size && trafoDepth < maxTrafoDepth && !(intra_split && trafoDepth == 0);
+    return (coded ? HAVOC_INTRA_RATE_SPLIT_FLAG_CODED : 0) | (trafoDepth ? HAVOC_INTRA_RATE_DEPTH_NONZERO : 0);
+}
+
+} // extern "C"
+
+namespace {
+
+int intraDevice(havoc_mi355x_ctx *ctx, int S, int bitDepth, const void *d_src, intptr_t src_stride, const havoc_intra_group *groups, int ngroups, const uint8_t *d_states,
+                const havoc_rqt_quant quant[4], double reciprocal_sqrt_lambda, double lambda, double reciprocal_lambda, int sdh, havoc_rqt_stats *stats, const RatedApi *api,
+                const uint8_t *d_syntax_states, const int32_t *flags)
+{
     if (!ctx || !d_src || !groups || ngroups < 0 || ngroups > 16 || !d_states || !quant || (S != 1 && S != 2)) return HAVOC_MI355X_EINVAL;
     const double tStart = now();
     havoc_rqt_stats st;
@@ -451,11 +528,28 @@ int havoc_search_intra_device(havoc_mi355x_ctx *ctx, int S, int bitDepth, const 
                              m, static_cast<int32_t *>(dCbf), dWork, havoc_mi355x_rdoq_workspace(m)));
         RC(havoc_mi355x_tu_reconstruct(ctx, S, bitDepth, tr, G.log2, q.inv_scale, q.inv_shift, dPiece, nn, dPred, nn, d_src, src_stride, static_cast<const int16_t *>(dLevel), tj,
                                        m, static_cast<uint32_t *>(dSsd)));
-        RC(havoc_mi355x_level_stats(ctx, static_cast<const int16_t *>(dLevel), static_cast<const int32_t *>(dSj), m, static_cast<int32_t *>(dStats)));
-        RC(havoc_mi355x_intra_decide(ctx, reinterpret_cast<const havoc_mi355x_intra_mpm *>(G.d_ictx), static_cast<const int32_t *>(w.dOrder),
-                                     static_cast<const int32_t *>(w.dCount), static_cast<const int32_t *>(w.dSlot), static_cast<const int32_t *>(dCbf),
-                                     static_cast<const uint32_t *>(dSsd), static_cast<const int32_t *>(dStats), tj, G.n, G.log2, rl.value,
-                                     static_cast<havoc_mi355x_intra_choice *>(vOut), static_cast<havoc_mi355x_tu_fused_job *>(dFin)));
+        const havoc_mi355x_intra_mpm *mpm = reinterpret_cast<const havoc_mi355x_intra_mpm *>(G.d_ictx);
+        if (api)
+        {
+            void *dRateJobs, *dRates;
+            RC(arena.get(size_t(m) * sizeof(havoc_mi355x_intra_rate_job), &dRateJobs, &hx));
+            RC(arena.get(size_t(m) * 8, &dRates, &hx));
+            RC(api->rateJobs(ctx, mpm, static_cast<const int32_t *>(w.dOrder), static_cast<const int32_t *>(w.dCount), static_cast<const int32_t *>(w.dSlot),
+                             static_cast<const havoc_mi355x_rdoq_job *>(dRj), G.n, flags[g], static_cast<havoc_mi355x_intra_rate_job *>(dRateJobs)));
+            RC(api->rate(ctx, G.log2, static_cast<const int16_t *>(dLevel), d_states, d_syntax_states, static_cast<const havoc_mi355x_intra_rate_job *>(dRateJobs), m,
+                         static_cast<int64_t *>(dRates), nullptr, nullptr));
+            RC(api->decideRated(ctx, mpm, static_cast<const int32_t *>(w.dOrder), static_cast<const int32_t *>(w.dCount), static_cast<const int32_t *>(w.dSlot),
+                                static_cast<const int32_t *>(dCbf), static_cast<const uint32_t *>(dSsd), nullptr, static_cast<const int64_t *>(dRates), tj, G.n, G.log2,
+                                rl.value, static_cast<havoc_mi355x_intra_choice *>(vOut), static_cast<havoc_mi355x_tu_fused_job *>(dFin)));
+            ++st.launches;
+        }
+        else
+        {
+            RC(havoc_mi355x_level_stats(ctx, static_cast<const int16_t *>(dLevel), static_cast<const int32_t *>(dSj), m, static_cast<int32_t *>(dStats)));
+            RC(havoc_mi355x_intra_decide(ctx, mpm, static_cast<const int32_t *>(w.dOrder), static_cast<const int32_t *>(w.dCount), static_cast<const int32_t *>(w.dSlot),
+                                         static_cast<const int32_t *>(dCbf), static_cast<const uint32_t *>(dSsd), static_cast<const int32_t *>(dStats), tj, G.n, G.log2,
+                                         rl.value, static_cast<havoc_mi355x_intra_choice *>(vOut), static_cast<havoc_mi355x_tu_fused_job *>(dFin)));
+        }
         RC(havoc_mi355x_tu_reconstruct(ctx, S, bitDepth, tr, G.log2, q.inv_scale, q.inv_shift, G.d_rec, nn, dPred, nn, d_src, src_stride, static_cast<const int16_t *>(dLevel),
                                        static_cast<const havoc_mi355x_tu_fused_job *>(dFin), G.n, static_cast<uint32_t *>(dSsd2)));
         st.launches += 8;
@@ -471,6 +565,10 @@ int havoc_search_intra_device(havoc_mi355x_ctx *ctx, int S, int bitDepth, const 
     if (stats) *stats = st;
     return 0;
 }
+
+} // namespace
+
+extern "C" {
 
 // An INTRA picture with the real dependencies between its partitions (turing/Reconstruct.cpp:609-615: a partition predicts from the reconstruction of the ones before
 // it; CandModeList.h:33-95: its most probable modes are its neighbours' champions), level by level WITHOUT a wait between the levels: per level and size
