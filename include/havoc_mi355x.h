@@ -731,6 +731,42 @@ typedef struct {
 int havoc_mi355x_intra_rate(havoc_mi355x_ctx *ctx, int log2TrafoSize, const int16_t *d_levels, const uint8_t *d_states, const uint8_t *d_syntax_states,
                             const havoc_mi355x_intra_rate_job *d_jobs, int njobs, int64_t *d_rate, uint8_t *d_states_out, uint8_t *d_syntax_states_out);
 
+/* ---- the CABAC rate of an inter unit's whole transform tree at one depth (csrc/kernels_residual_rate.hip: k_tree_rate) ----
+ * What the inter transform-tree decision compares (turing/Reconstruct.cpp:1296-1428): EstimateRate<void> over `if (rqt_root_cbf) transform_tree` of an inter 2Nx2N coding
+ * unit of log2 size L = log2CbSize in {3, 4, 5}, coded at `depth` 0 (one transform unit) or 1 (four), with ONE CABAC state running through split_transform_flag, cbf_cb,
+ * cbf_cr, cbf_luma and the Y, Cb and Cr residual_coding (Syntax<transform_tree>, turing/SyntaxCtu.hpp:329-379; Syntax<transform_unit>, :411-502; the writers,
+ * turing/Binarization.h:617-666).  rqt_root_cbf itself is NOT priced.  Preconditions (turing/Encoder.cpp:662-666 with the residual quadtree on): MaxTrafoDepth 1 for
+ * inter, MinTbLog2SizeY 2, MaxTbLog2SizeY >= L, 4:2:0, CuPredMode MODE_INTER, scanIdx 0, and cu_qp_delta_enabled_flag, cu_chroma_qp_offset_enabled_flag,
+ * cross_component_prediction_enabled_flag, transform_skip_enabled_flag, cu_transquant_bypass_flag all 0.  One launch = one (L, depth); one job = one candidate tree:
+ *   depth 0: split_transform_flag = 0 (ctxInc 5 - L) where coded; cbf_cb, cbf_cr (ctxInc 0); cbf_luma (ctxInc 1) ONLY when cbf_cb || cbf_cr (else inferred 1, no bin);
+ *            residual_coding of the Y block (log2 L), the Cb block and the Cr block (log2 max(L - 1, 2));
+ *   depth 1: split_transform_flag = 1 (ctxInc 5 - L) where coded; the parent's cbf_cb, cbf_cr (ctxInc 0): the OR of the children's, for L == 3 the one 4x4 block's own;
+ *            per child k = 0..3 in z-order, without a split flag: for L > 3 cbf_cb (ctxInc 1) only if the parent's is 1, the same for cbf_cr; cbf_luma (ctxInc 0), always;
+ *            the child's Y block (log2 L - 1); for L > 3 its Cb and then its Cr block (log2 L - 2); for L == 3 after child 3 ONLY the parent's 4x4 Cb and then Cr block.
+ * cbf_cb and cbf_cr share the contexts at HAVOC_RDOQ_CTX_CBF_CHROMA, Cb and Cr residuals the chroma residual contexts: the order Cb0 Cr0 Cb1 Cr1 ... is the syntax's.
+ * A tree with no level in any plane (rqt_root_cbf = 0) costs 0 and moves no context.  split_transform_flag's contexts are in the 4-byte syntax snapshot
+ * (HAVOC_INTRA_SYNTAX_CTX_SPLIT_TRANSFORM_FLAG; its first byte passes through), everything else in the 128-byte one.
+ * d_rate[out_index]: the Q16 Cost.  d_cbf[out_index]: bit k = Y block k has a level, bit 4 + k = Cb block k, bit 8 + k = Cr block k (depth 0, and the chroma of L == 3, use
+ * k = 0 only).  d_states_out / d_syntax_states_out: NULL, or njobs x 128 / njobs x 4 bytes: job j's snapshots as its walk left them (an all-zero tree: its input).
+ * For L in {3, 4, 5} the syntax can code split_transform_flag at every size, so no flag value is impossible; a job whose `flags` has a bit other than
+ * HAVOC_TREE_RATE_SPLIT_FLAG_CODED cannot be walked: no level of it is read, d_rate = -1, d_cbf = 0, its output snapshots are its input.  The flag itself is TRUSTED: the
+ * kernel sees neither MaxTbLog2SizeY nor MaxTrafoDepth, so a caller who sets it for a unit whose split is inferred (a 32x32 unit above MaxTbLog2SizeY, interSplitFlag) gets
+ * the price of a bin the syntax does not code, and no refusal.  The offsets and indices are trusted: luma_off, cb_off and cr_off are multiples of 4 (the levels are read
+ * as 8-byte rows).  The inputs are never written.  d_luma_levels, d_chroma_levels and d_rate 8-byte aligned, d_cbf 4-byte.  EINVAL: log2CbSize outside 3..5, depth outside 0..1,
+ * njobs < 0, a null input or d_rate / d_cbf, an output snapshot table that is its input.  No allocation, no synchronisation, no workspace: capturable into a HIP graph. */
+enum { HAVOC_TREE_RATE_SPLIT_FLAG_CODED = 1 };   /* split_transform_flag of the unit is coded (as `depth`) */
+typedef struct {
+    int32_t luma_off;        /* in d_luma_levels: depth 0 the unit's n*n block; depth 1 four (n/2)^2 blocks, contiguous, z-order; int16 raster; multiple of 4 */
+    int32_t cb_off, cr_off;  /* in d_chroma_levels: depth 0, or n == 8: one block of c*c, c = max(n/2, 4); depth 1 and n > 8: four (n/4)^2 blocks, contiguous, z-order; multiples of 4 */
+    int32_t ctx_index;       /* the snapshot of d_states (128 bytes) and of d_syntax_states (4 bytes) the tree starts from */
+    int32_t out_index;       /* d_rate[out_index], d_cbf[out_index] */
+    uint8_t sdh, flags, pad[2];   /* sign_data_hiding_enabled_flag; HAVOC_TREE_RATE_* */
+    int32_t reserved[2];
+} havoc_mi355x_tree_rate_job;   /* sizeof: 32 */
+int havoc_mi355x_tree_rate(havoc_mi355x_ctx *ctx, int log2CbSize, int depth, const int16_t *d_luma_levels, const int16_t *d_chroma_levels, const uint8_t *d_states,
+                           const uint8_t *d_syntax_states, const havoc_mi355x_tree_rate_job *d_jobs, int njobs, int64_t *d_rate, uint32_t *d_cbf,
+                           uint8_t *d_states_out, uint8_t *d_syntax_states_out);
+
 /* The same two steps with the scan of the coefficients done where they are produced (16x16 / 32x32 blocks; round 3):
  *   tu_forward_scan  = tu_forward + the first pass of the device RDOQ (which 4x4 groups hold a rounded level, the block's energy -> d_work;
  *                      the level block of d_rdoq_jobs[i].dst_off zeroed).  d_rdoq_jobs[i] describes the same block as d_jobs[i]
@@ -821,10 +857,29 @@ int havoc_mi355x_rqt_decide(havoc_mi355x_ctx *ctx, const havoc_mi355x_rqt_unit *
 /* The same decision with the residual term supplied: d_rates[s - 2][j] = the Q16 rate of candidate j of transform size s (havoc_mi355x_residual_rate: the reference's
  * bits of its residual_coding) in place of the stand-in; a size with tables has its rates.  Order of evaluation, the uncoded short-cut, the Q16 arithmetic, `cost_zero < cost_one`,
  * the final job records and the 104-byte results are havoc_mi355x_rqt_decide's.  sizes[k].d_stats may be NULL: nonzero / sum_abs of the results are then 0.  With real
- * residual rates the costs still leave out what the reference charges beside them: cbf_luma, split_transform_flag and the chroma residuals of the tree. */
+ * residual rates the costs still leave out what the reference charges beside them: cbf_luma, split_transform_flag and the chroma residuals of the tree, and weigh luma
+ * distortion only; havoc_mi355x_rqt_decide_tree below compares what the reference compares. */
 int havoc_mi355x_rqt_decide_rated(havoc_mi355x_ctx *ctx, const havoc_mi355x_rqt_unit *d_units, int n, const int32_t *d_zero_at, const int32_t *d_one_at,
                                   const havoc_mi355x_rqt_size sizes[4], const int64_t *const d_rates[4], int64_t rec_origin, intptr_t rec_stride, int32_t dump_off,
                                   int32_t reciprocal_lambda_q16, havoc_mi355x_rqt_choice *d_out);
+/* The reference's own decision over three planes (turing/Reconstruct.cpp:1325-1424): depth 1 first; its rqt_root_cbf 0 -- no level in ANY of Y, Cb, Cr -- leaves the unit
+ * unsplit without residual and depth 0 untried; else  cost_d = rate_d + (ssdY + 4 ssdCb + 4 ssdCr) * reciprocal_lambda  with the sum in int32 (StateEncodeSubstream::ssd) and
+ * depth 0 winning on cost_zero < cost_one.  rate_d = d_tree_rate[2 * i + d], the whole transform_tree's bits of unit i at depth d, and d_tree_cbf[2 * i + d] its mask, both as
+ * havoc_mi355x_tree_rate writes them (out_index = 2 * i + d).  Luma candidates: sizes / d_zero_at / d_one_at as in havoc_mi355x_rqt_decide (d_stats may be NULL).  Chroma
+ * candidates: csizes[c - 2] holds the Cb and Cr candidates of chroma transform size c the same way (d_cbf, d_ssd, d_jobs, d_final; d_stats is not read); d_chroma_at[i] says
+ * where unit i's are: its depth-0 Cb / Cr candidate in csizes[max(L - 1, 2) - 2], and for L > 3 the first of its four depth-1 Cb / Cr candidates (z-order, one after the
+ * other) in csizes[L - 4]; an 8x8 unit's one 4x4 block per component is the same candidate at both depths (cb_one / cr_one are not read).
+ *   d_out: havoc_mi355x_rqt_choice as before -- the luma outcomes, depth, tried_zero -- with cost_zero / cost_one the whole-tree costs; havoc_mi355x_block_cells reads it
+ * unchanged.  d_tree_out: the masks and the sums ssdCb + ssdCr of both depths (depth 0's are 0 when it was not tried).  d_final of every luma AND chroma candidate: a
+ * candidate of the chosen tree goes into the picture (luma: rec_origin + y * rec_stride + x; Cb / Cr: cb_origin / cr_origin + (y / 2) * c_stride + x / 2), every other to
+ * dump_off / c_dump_off; a unit left without residual is reconstructed through its depth-1 candidates, whose levels are all zero. */
+typedef struct { int32_t cb_zero, cr_zero, cb_one, cr_one; } havoc_mi355x_rqt_chroma_at;     /* 16 bytes */
+typedef struct { uint32_t mask_zero, mask_one; int32_t chroma_ssd_zero, chroma_ssd_one; } havoc_mi355x_rqt_tree_choice;     /* 16 bytes */
+int havoc_mi355x_rqt_decide_tree(havoc_mi355x_ctx *ctx, const havoc_mi355x_rqt_unit *d_units, int n, const int32_t *d_zero_at, const int32_t *d_one_at,
+                                 const havoc_mi355x_rqt_size sizes[4], const havoc_mi355x_rqt_size csizes[4], const havoc_mi355x_rqt_chroma_at *d_chroma_at,
+                                 const int64_t *d_tree_rate, const uint32_t *d_tree_cbf, int64_t rec_origin, intptr_t rec_stride, int32_t dump_off,
+                                 int64_t cb_origin, int64_t cr_origin, intptr_t c_stride, int32_t c_dump_off, int32_t reciprocal_lambda_q16,
+                                 havoc_mi355x_rqt_choice *d_out, havoc_mi355x_rqt_tree_choice *d_tree_out);
 /* the 4x4 cells havoc_mi355x_derive_bs reads, made from the decisions: every unit one inter 2Nx2N prediction unit from list 0 (decoded picture dpb_index0) at the vector d_field
  * (int16 [2][height / 4][width / 4][2]) holds at its origin, coded flags and transform sizes as decided; cells outside the units: no motion coded, qp, tu_log2 = 2 */
 int havoc_mi355x_block_cells(havoc_mi355x_ctx *ctx, int width, int height, int qp, int dpb_index0, const int16_t *d_field, const havoc_mi355x_rqt_unit *d_units,

@@ -29,9 +29,11 @@ static_assert(sizeof(havoc_mi355x_sao_decision) == 128 && offsetof(havoc_mi355x_
 static_assert(sizeof(havoc_mi355x_residual_rate_job) == 32 && offsetof(havoc_mi355x_residual_rate_job, c_idx) == 12, "job ABI");
 static_assert(sizeof(havoc_mi355x_intra_rate_job) == 32 && offsetof(havoc_mi355x_intra_rate_job, scan_idx) == 12 && offsetof(havoc_mi355x_intra_rate_job, flags) == 15,
               "job ABI");
+static_assert(sizeof(havoc_mi355x_tree_rate_job) == 32 && offsetof(havoc_mi355x_tree_rate_job, out_index) == 16 && offsetof(havoc_mi355x_tree_rate_job, flags) == 21, "job ABI");
 static_assert(sizeof(havoc_mi355x_intra_mpm) == 40 && sizeof(havoc_mi355x_intra_choice) == 40, "job ABI");
 static_assert(sizeof(havoc_mi355x_rdoq_job) == 48 && offsetof(havoc_mi355x_rdoq_job, c_idx) == 32, "job ABI");
 static_assert(sizeof(havoc_mi355x_sad4_run) == 32 && sizeof(havoc_mi355x_sao_stats_job) == 16 && sizeof(havoc_mi355x_sao_chroma_job) == 32 && sizeof(havoc_mi355x_sao_job) == 96, "job ABI");
+static_assert(sizeof(havoc_mi355x_rqt_chroma_at) == 16 && sizeof(havoc_mi355x_rqt_tree_choice) == 16, "record ABI");
 static_assert(sizeof(havoc_mi355x_rqt_unit) == 16 && sizeof(havoc_mi355x_tu_outcome) == 16 && sizeof(havoc_mi355x_rqt_choice) == 104 && sizeof(havoc_mi355x_rqt_size) == 40 &&
               sizeof(havoc_mi355x_cell) == 16 && offsetof(havoc_mi355x_cell, qp_y) == 11, "record ABI");
 static_assert(sizeof(havoc_mi355x_intra_chain_part) == 16 && sizeof(havoc_mi355x_intra_chain_layout) == 32 && sizeof(havoc_mi355x_field_layout) == 48, "record ABI");
@@ -730,6 +732,30 @@ int havoc_mi355x_rqt_decide_rated(havoc_mi355x_ctx *ctx, const havoc_mi355x_rqt_
                  "rqt_decide_rated");
 }
 
+int havoc_mi355x_rqt_decide_tree(havoc_mi355x_ctx *ctx, const havoc_mi355x_rqt_unit *d_units, int n, const int32_t *d_zero_at, const int32_t *d_one_at,
+                                 const havoc_mi355x_rqt_size sizes[4], const havoc_mi355x_rqt_size csizes[4], const havoc_mi355x_rqt_chroma_at *d_chroma_at,
+                                 const int64_t *d_tree_rate, const uint32_t *d_tree_cbf, int64_t rec_origin, intptr_t rec_stride, int32_t dump_off,
+                                 int64_t cb_origin, int64_t cr_origin, intptr_t c_stride, int32_t c_dump_off, int32_t reciprocal_lambda_q16,
+                                 havoc_mi355x_rqt_choice *d_out, havoc_mi355x_rqt_tree_choice *d_tree_out)
+{
+    REQUIRE_CTX(); REQUIRE(n >= 0, "n < 0"); REQUIRE(sizes != nullptr && csizes != nullptr, "null sizes");
+    REQUIRE(rec_stride > 0 && rec_stride < (1 << 24), "rec_stride out of range"); REQUIRE(c_stride > 0 && c_stride < (1 << 24), "c_stride out of range");
+    REQUIRE(n == 0 || (d_units && d_zero_at && d_one_at && d_chroma_at && d_tree_rate && d_tree_cbf && d_out && d_tree_out), "null device pointer");
+    REQUIRE(reciprocal_lambda_q16 >= 0, "reciprocal_lambda_q16 < 0"); REQUIRE(dump_off >= 0 && c_dump_off >= 0, "dump_off < 0");
+    REQUIRE(cb_origin >= 0 && cr_origin >= 0 && rec_origin >= 0, "origin < 0");
+    if (n > 0)      // as havoc_mi355x_rqt_decide_rated: d_stats may be null; a chroma table (sizes 4 .. 16 = csizes[0 .. 2]) is whole or absent
+        for (int k = 0; k < 4; ++k)
+        {
+            const havoc_mi355x_rqt_size &z = sizes[k], &c = csizes[k];
+            const bool all = z.d_cbf && z.d_ssd && z.d_jobs && z.d_final, none = !z.d_cbf && !z.d_ssd && !z.d_stats && !z.d_jobs && !z.d_final;
+            REQUIRE(all || none, "rqt_decide_tree: a size table with some null pointers");
+            const bool call = c.d_cbf && c.d_ssd && c.d_jobs && c.d_final, cnone = !c.d_cbf && !c.d_ssd && !c.d_stats && !c.d_jobs && !c.d_final;
+            REQUIRE(call || cnone, "rqt_decide_tree: a chroma size table with some null pointers");
+        }
+    return check(launch_rqt_decide_tree(LS(ctx), d_units, n, d_zero_at, d_one_at, sizes, csizes, d_chroma_at, d_tree_rate, d_tree_cbf, (long)rec_origin, (int)rec_stride, dump_off,
+                                        (long)cb_origin, (long)cr_origin, (int)c_stride, c_dump_off, reciprocal_lambda_q16, d_out, d_tree_out), "rqt_decide_tree");
+}
+
 int havoc_mi355x_block_cells(havoc_mi355x_ctx *ctx, int width, int height, int qp, int dpb_index0, const int16_t *d_field, const havoc_mi355x_rqt_unit *d_units,
                              const havoc_mi355x_rqt_choice *d_decisions, int n, havoc_mi355x_cell *d_cells)
 {
@@ -1044,6 +1070,21 @@ int havoc_mi355x_intra_rate(havoc_mi355x_ctx *ctx, int log2TrafoSize, const int1
     REQUIRE(d_states_out != d_states, "intra_rate: d_states_out must not be d_states (which is never written)");
     REQUIRE(d_syntax_states_out != d_syntax_states, "intra_rate: d_syntax_states_out must not be d_syntax_states (which is never written)");
     return check(launch_intra_rate(LS(ctx), log2TrafoSize, d_levels, d_states, d_syntax_states, d_jobs, njobs, d_rate, d_states_out, d_syntax_states_out), "intra_rate");
+}
+
+int havoc_mi355x_tree_rate(havoc_mi355x_ctx *ctx, int log2CbSize, int depth, const int16_t *d_luma_levels, const int16_t *d_chroma_levels, const uint8_t *d_states,
+                           const uint8_t *d_syntax_states, const havoc_mi355x_tree_rate_job *d_jobs, int njobs, int64_t *d_rate, uint32_t *d_cbf,
+                           uint8_t *d_states_out, uint8_t *d_syntax_states_out)
+{
+    REQUIRE_CTX(); REQUIRE(log2CbSize >= 3 && log2CbSize <= 5, "tree_rate: log2CbSize must be 3..5"); REQUIRE(depth == 0 || depth == 1, "tree_rate: depth must be 0 or 1");
+    REQUIRE(njobs >= 0, "njobs < 0");
+    REQUIRE(d_luma_levels && d_chroma_levels && d_states && d_syntax_states && d_jobs && d_rate && d_cbf, "tree_rate: null device pointer");
+    REQUIRE((reinterpret_cast<uintptr_t>(d_luma_levels) & 7) == 0 && (reinterpret_cast<uintptr_t>(d_chroma_levels) & 7) == 0 && (reinterpret_cast<uintptr_t>(d_rate) & 7) == 0 &&
+            (reinterpret_cast<uintptr_t>(d_cbf) & 3) == 0, "tree_rate: d_luma_levels, d_chroma_levels and d_rate must be 8-byte aligned, d_cbf 4-byte");
+    REQUIRE(d_states_out != d_states, "tree_rate: d_states_out must not be d_states (which is never written)");
+    REQUIRE(d_syntax_states_out != d_syntax_states, "tree_rate: d_syntax_states_out must not be d_syntax_states (which is never written)");
+    return check(launch_tree_rate(LS(ctx), log2CbSize, depth, d_luma_levels, d_chroma_levels, d_states, d_syntax_states, d_jobs, njobs, d_rate, d_cbf, d_states_out,
+                                  d_syntax_states_out), "tree_rate");
 }
 
 } // extern "C"

@@ -182,7 +182,8 @@ __global__ __launch_bounds__(256) void k_intra_decide(const IntraCtx *__restrict
 // search/tu_decision.hpp's decideRqt (turing/Reconstruct.cpp:1296-1428) restated lane per unit over the outcomes of its five candidate blocks (depth 0: one block,
 // depth 1: four, evaluated by the chain tu_forward -> rdoq -> tu_reconstruct -> level_stats), so that a picture's launches after its searches need no host in
 // between (the residual term is the stand-in of tu_decision.hpp, or -- RATED -- the reference's bits of each candidate's residual_coding from
-// kernels_residual_rate.hip; cbf_luma, split_transform_flag and the chroma residuals are priced by neither): the decision, the job records that reconstruct EVERY candidate -- the chosen ones into the picture, the others into a dump area (a fixed number of jobs per
+// kernels_residual_rate.hip; cbf_luma, split_transform_flag and the chroma residuals are priced by neither -- or, kRqtTree, the reference's whole comparison over three
+// planes from havoc_mi355x_tree_rate): the decision, the job records that reconstruct EVERY candidate -- the chosen ones into the picture, the others into a dump area (a fixed number of jobs per
 // size: the sequence can be recorded into a HIP graph) -- and the 4x4 cells havoc_mi355x_derive_bs reads.  The host forms stay: tests hold these against them.
 using RqtUnit = havoc_mi355x_rqt_unit;
 using TuOutcome = havoc_mi355x_tu_outcome;
@@ -193,17 +194,34 @@ struct RqtSizes { RqtSize s[4]; };
 
 struct RqtRates { const int64_t *r[4]; };      // havoc_mi355x_rqt_decide_rated: the Q16 rate of candidate j of each transform size
 
+// havoc_mi355x_rqt_decide_tree: the chroma candidates per chroma transform size, where each unit finds its own, the whole-tree rate and cbf mask per unit and depth
+// (havoc_mi355x_tree_rate), the chroma reconstruction planes and the 16-byte records
+struct RqtTree
+{
+    RqtSizes c;
+    const havoc_mi355x_rqt_chroma_at *at;
+    const int64_t *rate;
+    const uint32_t *cbf;
+    long cbOrigin, crOrigin;
+    int cStride, cDump;
+    havoc_mi355x_rqt_tree_choice *out;
+};
+
+enum RqtMode { kRqtStandIn, kRqtRated, kRqtTree };
+
 __device__ __forceinline__ TuOutcome outcomeOf(const RqtSize &z, int j)
 {
     return z.d_stats ? TuOutcome{z.d_cbf[j], z.d_ssd[j], z.d_stats[2 * j], z.d_stats[2 * j + 1]} : TuOutcome{z.d_cbf[j], z.d_ssd[j], 0, 0};      // (no level statistics: the rated form)
 }
 __device__ __forceinline__ int64_t tuRateOf(const TuOutcome &t) { return (int64_t)(1 + (t.cbf ? 2 * t.nonzero + t.sum_abs : 0)) << 16; }      // tu_decision.hpp: tuRate (stand-in)
 
-// RATED: the residual term is the caller's rate of each candidate (havoc_mi355x_residual_rate: the reference's bits) in place of the stand-in; nothing else differs
-template <bool RATED>
+// kRqtRated: the residual term is the caller's rate of each candidate (havoc_mi355x_residual_rate: the reference's bits) in place of the stand-in; nothing else differs.
+// kRqtTree: the reference's own comparison -- the rate is the whole transform_tree's of the depth (havoc_mi355x_tree_rate), the distortion ssdY + 4 ssdCb + 4 ssdCr in
+// int32, "coded" means a level in any of the three planes -- and the chroma candidates get their final job records beside the luma ones.
+template <int MODE>
 __global__ __launch_bounds__(256) void k_rqt_decide(const RqtUnit *__restrict__ units, int n, const int32_t *__restrict__ zeroAt, const int32_t *__restrict__ oneAt,
-                                                    const RqtSizes z, const RqtRates rates, long recOrigin, int recStride, int dumpOff, int32_t reciprocalLambdaQ16,
-                                                    RqtResult *__restrict__ out)
+                                                    const RqtSizes z, const RqtRates rates, const RqtTree tree, long recOrigin, int recStride, int dumpOff,
+                                                    int32_t reciprocalLambdaQ16, RqtResult *__restrict__ out)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -213,10 +231,17 @@ __global__ __launch_bounds__(256) void k_rqt_decide(const RqtUnit *__restrict__ 
         RqtResult bad = RqtResult();
         bad.depth = -1;
         out[i] = bad;
+        if (MODE == kRqtTree) tree.out[i] = havoc_mi355x_rqt_tree_choice();
         return;
     }
     const RqtSize &s0 = z.s[u.log2_size - 2], &s1 = z.s[u.log2_size - 3];
     const int j0 = zeroAt[i], j1 = oneAt[i], half = 1 << (u.log2_size - 1);
+    // the unit's chroma candidates (kRqtTree): depth 0 one Cb and one Cr block of log2 max(L - 1, 2); depth 1 four of each of log2 L - 2 -- an 8x8 unit's one 4x4
+    // block per component is the same candidate at both depths
+    const int chromaOne = u.log2_size > 3 ? 4 : 0;
+    const RqtSize &c0 = tree.c.s[u.log2_size > 3 ? u.log2_size - 3 : 0], &c1 = tree.c.s[u.log2_size > 3 ? u.log2_size - 4 : 0];
+    havoc_mi355x_rqt_chroma_at ca = havoc_mi355x_rqt_chroma_at();
+    havoc_mi355x_rqt_tree_choice tc = havoc_mi355x_rqt_tree_choice();
     RqtResult r = RqtResult();
     int32_t ssdOne = 0;      // (int32 as the reference's StateEncodeSubstream::ssd: four 16x16 blocks of <= 255^2 * 256 each, or 10-bit SSDs >> 4, stay far below 2^31)
     bool coded = false;
@@ -226,17 +251,44 @@ __global__ __launch_bounds__(256) void k_rqt_decide(const RqtUnit *__restrict__ 
         r.one[k] = outcomeOf(s1, j1 + k);
         ssdOne += (int32_t)r.one[k].ssd;
         coded |= r.one[k].cbf != 0;
-        rateOne += RATED ? rates.r[u.log2_size - 3][j1 + k] : tuRateOf(r.one[k]);
+        if (MODE != kRqtTree) rateOne += MODE == kRqtRated ? rates.r[u.log2_size - 3][j1 + k] : tuRateOf(r.one[k]);
+    }
+    if (MODE == kRqtTree)
+    {
+        ca = tree.at[i];
+        uint32_t chroma = 0;
+        if (chromaOne)
+            for (int k = 0; k < 4; ++k) chroma += c1.d_ssd[ca.cb_one + k] + c1.d_ssd[ca.cr_one + k];
+        else
+            chroma = c0.d_ssd[ca.cb_zero] + c0.d_ssd[ca.cr_zero];
+        tc.chroma_ssd_one = (int32_t)chroma;
+        tc.mask_one = tree.cbf[2 * i + 1];
+        ssdOne = (int32_t)((uint32_t)ssdOne + 4u * chroma);      // ssd[0] + 4 ssd[1] + 4 ssd[2], int32
+        coded = tc.mask_one != 0;                                 // rqt_root_cbf of the split tree: a level in ANY plane
+        rateOne = tree.rate[2 * i + 1];
     }
     r.cost_one = rateOne + (int64_t)reciprocalLambdaQ16 * (int64_t)ssdOne;
     if (coded)
     {
         r.tried_zero = 1;
         r.zero = outcomeOf(s0, j0);
-        r.cost_zero = (RATED ? rates.r[u.log2_size - 2][j0] : tuRateOf(r.zero)) + (int64_t)reciprocalLambdaQ16 * (int64_t)(int32_t)r.zero.ssd;
+        int32_t ssdZero = (int32_t)r.zero.ssd;
+        int64_t rateZero = 0;
+        if (MODE == kRqtTree)
+        {
+            const uint32_t chroma = c0.d_ssd[ca.cb_zero] + c0.d_ssd[ca.cr_zero];
+            tc.chroma_ssd_zero = (int32_t)chroma;
+            tc.mask_zero = tree.cbf[2 * i];
+            ssdZero = (int32_t)((uint32_t)ssdZero + 4u * chroma);
+            rateZero = tree.rate[2 * i];
+        }
+        else
+            rateZero = MODE == kRqtRated ? rates.r[u.log2_size - 2][j0] : tuRateOf(r.zero);
+        r.cost_zero = rateZero + (int64_t)reciprocalLambdaQ16 * (int64_t)ssdZero;
         r.depth = r.cost_zero < r.cost_one ? 0 : 1;      // Reconstruct.cpp:1389
     }
     out[i] = r;
+    if (MODE == kRqtTree) tree.out[i] = tc;
     // every candidate is reconstructed once more: the chosen tree into the picture -- a unit left without residual through its four depth-1 blocks, whose levels are
     // all zero (= the prediction) -- the rest into the dump area
     const bool zeroWins = r.depth == 0 && r.tried_zero;
@@ -248,6 +300,27 @@ __global__ __launch_bounds__(256) void k_rqt_decide(const RqtUnit *__restrict__ 
         TuJob g = s1.d_jobs[j1 + k];
         g.rec_off = zeroWins ? dumpOff : (int32_t)(recOrigin + (long)(u.y0 + (k >> 1) * half) * recStride + u.x0 + (k & 1) * half);
         s1.d_final[j1 + k] = g;
+    }
+    if (MODE == kRqtTree)
+    {   // ... and the chroma candidates into the chroma reconstruction planes the same way (an 8x8 unit's only chroma candidate belongs to both trees)
+        const long at = (long)(u.y0 >> 1) * tree.cStride + (u.x0 >> 1);
+        const bool zeroChroma = zeroWins || !chromaOne;
+        TuJob cb = c0.d_jobs[ca.cb_zero], cr = c0.d_jobs[ca.cr_zero];
+        cb.rec_off = zeroChroma ? (int32_t)(tree.cbOrigin + at) : tree.cDump;
+        cr.rec_off = zeroChroma ? (int32_t)(tree.crOrigin + at) : tree.cDump;
+        c0.d_final[ca.cb_zero] = cb;
+        c0.d_final[ca.cr_zero] = cr;
+        const int quarter = half >> 1;
+        for (int k = 0; k < chromaOne; ++k)
+        {
+            const long sub = at + (long)((k >> 1) * quarter) * tree.cStride + (k & 1) * quarter;
+            cb = c1.d_jobs[ca.cb_one + k];
+            cr = c1.d_jobs[ca.cr_one + k];
+            cb.rec_off = zeroWins ? tree.cDump : (int32_t)(tree.cbOrigin + sub);
+            cr.rec_off = zeroWins ? tree.cDump : (int32_t)(tree.crOrigin + sub);
+            c1.d_final[ca.cb_one + k] = cb;
+            c1.d_final[ca.cr_one + k] = cr;
+        }
     }
 }
 
@@ -296,10 +369,22 @@ hipError_t launch_rqt_decide(hipStream_t st, const RqtUnit *units, int n, const 
     if (n <= 0) return hipSuccess;
     const RqtSizes z{{sizes[0], sizes[1], sizes[2], sizes[3]}};
     if (rates)
-        hipLaunchKernelGGL(k_rqt_decide<true>, dim3((n + 255) / 256), dim3(256), 0, st, units, n, zeroAt, oneAt, z,
-                           RqtRates{{rates[0], rates[1], rates[2], rates[3]}}, recOrigin, recStride, dumpOff, rlQ16, out);
+        hipLaunchKernelGGL(k_rqt_decide<kRqtRated>, dim3((n + 255) / 256), dim3(256), 0, st, units, n, zeroAt, oneAt, z,
+                           RqtRates{{rates[0], rates[1], rates[2], rates[3]}}, RqtTree(), recOrigin, recStride, dumpOff, rlQ16, out);
     else
-        hipLaunchKernelGGL(k_rqt_decide<false>, dim3((n + 255) / 256), dim3(256), 0, st, units, n, zeroAt, oneAt, z, RqtRates(), recOrigin, recStride, dumpOff, rlQ16, out);
+        hipLaunchKernelGGL(k_rqt_decide<kRqtStandIn>, dim3((n + 255) / 256), dim3(256), 0, st, units, n, zeroAt, oneAt, z, RqtRates(), RqtTree(), recOrigin, recStride, dumpOff,
+                           rlQ16, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_rqt_decide_tree(hipStream_t st, const RqtUnit *units, int n, const int32_t *zeroAt, const int32_t *oneAt, const RqtSize sizes[4], const RqtSize csizes[4],
+                                  const havoc_mi355x_rqt_chroma_at *chromaAt, const int64_t *treeRate, const uint32_t *treeCbf, long recOrigin, int recStride, int dumpOff,
+                                  long cbOrigin, long crOrigin, int cStride, int cDump, int32_t rlQ16, RqtResult *out, havoc_mi355x_rqt_tree_choice *treeOut)
+{
+    if (n <= 0) return hipSuccess;
+    const RqtSizes z{{sizes[0], sizes[1], sizes[2], sizes[3]}};
+    const RqtTree tree{{{csizes[0], csizes[1], csizes[2], csizes[3]}}, chromaAt, treeRate, treeCbf, cbOrigin, crOrigin, cStride, cDump, treeOut};
+    hipLaunchKernelGGL(k_rqt_decide<kRqtTree>, dim3((n + 255) / 256), dim3(256), 0, st, units, n, zeroAt, oneAt, z, RqtRates(), tree, recOrigin, recStride, dumpOff, rlQ16, out);
     return hipGetLastError();
 }
 

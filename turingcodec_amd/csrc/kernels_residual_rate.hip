@@ -1,5 +1,6 @@
 // k_residual_rate: the bits the reference's EstimateRate verb measures for one residual_coding, per transform block; k_intra_rate (below):
-// the same walk -- ONE device function, walkBlock -- behind the mode and transform-tree bins of an intra candidate.
+// the same walk -- ONE device function, walkBlock -- behind the mode and transform-tree bins of an intra candidate; k_tree_rate (last): the same walk over the
+// Y, Cb and Cr blocks of an inter unit's whole transform_tree at one depth, with split_transform_flag, cbf_cb, cbf_cr and cbf_luma beside them.
 //
 // Reference: EncodeResidual::inner<havePopcnt, is4x4, H> with H::Tag == EstimateRate<void> (turing/EncodeResidual.hpp:36-301) over the coded data
 // CodedData::storeResidual (turing/CodedData.h:457-517) packs from an n x n raster of levels; WriteLastSigPrefix / WriteLastSigSuffix
@@ -25,6 +26,7 @@ namespace {
 
 using RateJob = havoc_mi355x_residual_rate_job;
 using IntraRateJob = havoc_mi355x_intra_rate_job;
+using TreeRateJob = havoc_mi355x_tree_rate_job;
 
 enum { kLastX = HAVOC_RDOQ_CTX_LAST_X, kLastY = HAVOC_RDOQ_CTX_LAST_Y, kCsbf = HAVOC_RDOQ_CTX_CSBF, kSig = HAVOC_RDOQ_CTX_SIG, kG1 = HAVOC_RDOQ_CTX_GREATER1,
        kG2 = HAVOC_RDOQ_CTX_GREATER2 };
@@ -63,15 +65,32 @@ struct RateLds
     uint8_t st[128][64];        // the jobs' context states, [context][lane]
     int16_t lev[16][64];        // the current sub-block's levels, [raster position][lane]
     uint32_t cls[3][4];         // per scan and neighbour case: the scan positions whose sigPattern is 1 | those where it is 2, << 16
-    uint8_t subXy[64];          // the diagonal scan of the block's sub-blocks: x | y << 4
+    uint8_t subXy[3][64];       // the diagonal scan of the sub-blocks of an 8x8, 16x16, 32x32 block: x | y << 4 (a kernel fills the rows of the sizes it walks)
     int32_t ctxIndex[64];
 };
 
-// the tables every walk reads: the (state, bin) table, the sig_coeff_flag classes per scan and neighbour case, the diagonal scan of the sub-blocks
+// the diagonal scan of one block size's sub-blocks (ScanOrder.h:31-59 applied to the GW x GW sub-blocks); a 4x4 block has one sub-block and no row
+template <int LOG2>
+__device__ __forceinline__ void subBlockScan(RateLds &sh, int lane)
+{
+    constexpr int GW = (1 << LOG2) / 4, NSUB = GW * GW;
+    if (LOG2 >= 3 && lane < NSUB)
+    {
+        int pos = lane, x = 0, y = 0;
+        for (int d = 0; d < 2 * GW - 1; ++d)
+        {
+            const int lo = d < GW ? 0 : d - GW + 1, hi = d < GW ? d : GW - 1, len = hi - lo + 1;
+            if (pos < len) { x = lo + pos; y = d - x; break; }
+            pos -= len;
+        }
+        sh.subXy[LOG2 >= 3 ? LOG2 - 3 : 0][lane] = (uint8_t)(x | y << 4);
+    }
+}
+
+// the tables every walk reads: the (state, bin) table, the sig_coeff_flag classes per scan and neighbour case, the diagonal scan of the sub-blocks of the size LOG2
 template <int LOG2>
 __device__ __forceinline__ void rateTables(RateLds &sh, int lane)
 {
-    constexpr int GW = (1 << LOG2) / 4, NSUB = GW * GW;
     for (int k = lane; k < 256; k += 64) sh.bins[k] = bin_entry(k >> 1, k & 1);
     if (lane < 12)
     {
@@ -86,17 +105,7 @@ __device__ __forceinline__ void rateTables(RateLds &sh, int lane)
         }
         sh.cls[t][nb] = one | two << 16;
     }
-    if (lane < NSUB)
-    {   // ScanOrder.h:31-59 applied to the GW x GW sub-blocks
-        int pos = lane, x = 0, y = 0;
-        for (int d = 0; d < 2 * GW - 1; ++d)
-        {
-            const int lo = d < GW ? 0 : d - GW + 1, hi = d < GW ? d : GW - 1, len = hi - lo + 1;
-            if (pos < len) { x = lo + pos; y = d - x; break; }
-            pos -= len;
-        }
-        sh.subXy[lane] = (uint8_t)(x | y << 4);
-    }
+    subBlockScan<LOG2>(sh, lane);
 }
 
 // the workgroup's 64 snapshots into sh.st, transposed (sh.ctxIndex filled and a barrier passed before; one follows)
@@ -128,7 +137,7 @@ __device__ __forceinline__ int priceBin(RateLds &sh, int lane, int ctx, int bin)
 }
 
 // ONE residual_coding: the walk of a block's sub-blocks from the lane's states, which it moves -> its Q16 rate; coded = the block has a level (an all-zero
-// block: IfCbf skips it, rate 0, no context touched).  Both kernels of this file call it.
+// block: IfCbf skips it, rate 0, no context touched).  All three kernels of this file call it.
 template <int LOG2>
 __device__ __forceinline__ int64_t walkBlock(RateLds &sh, int lane, const int16_t *__restrict__ src, int cIdx, int scanIdx, int sdh, bool &coded)
 {
@@ -146,7 +155,7 @@ __device__ __forceinline__ int64_t walkBlock(RateLds &sh, int lane, const int16_
         {
             if (scanIdx == 1) { xS = i & (GW - 1); yS = i / GW; }
             else if (scanIdx == 2) { xS = i / GW; yS = i & (GW - 1); }
-            else { const int p = sh.subXy[i]; xS = p & 15; yS = p >> 4; }
+            else { const int p = sh.subXy[LOG2 >= 3 ? LOG2 - 3 : 0][i]; xS = p & 15; yS = p >> 4; }
         }
         const int16_t *sb = src + (yS * 4) * N + xS * 4;
         uint32_t any = 0;
@@ -351,7 +360,112 @@ __global__ __launch_bounds__(64) void k_intra_rate(const int16_t *__restrict__ l
     storeStates(sh.r, lane, first, njobs, statesOut);
 }
 
+// k_tree_rate: what the inter transform-tree decision measures per depth (turing/Reconstruct.cpp:1296-1428: EstimateRate<void> over `if (rqt_root_cbf) transform_tree`),
+// one candidate tree of one unit per lane in the form of the two kernels above; one launch per (log2CbSize L, depth), so that every lane of a launch walks the same
+// sequence of block sizes.  Syntax<transform_tree> (turing/SyntaxCtu.hpp:329-379) and Syntax<transform_unit> (:411-502) with MaxTrafoDepth 1, 4:2:0, scanIdx 0:
+//   depth 0: split_transform_flag = 0, cbf_cb, cbf_cr (both ctxInc 0), cbf_luma (ctxInc 1) only when cbf_cb || cbf_cr, then Y (log2 L), Cb, Cr (log2 max(L - 1, 2));
+//   depth 1: split_transform_flag = 1, the parent's cbf_cb, cbf_cr (ctxInc 0: the OR of the children's), then per child in z-order cbf_cb / cbf_cr (ctxInc 1, L > 3 and
+//            the parent's flag set), cbf_luma (ctxInc 0, always), Y (log2 L - 1), and Cb, Cr (log2 L - 2) -- for L == 3 the parent's one 4x4 Cb and Cr after child 3.
+// The residual blocks are walked FIRST, in the syntax's order (Cb and Cr share the chroma residual contexts: Cb0 Cr0 Cb1 Cr1 ...), which tells every cbf without a
+// second pass; the flag bins are priced after them, in the syntax's order among themselves (cbf_cb and cbf_cr share contexts).  The flag contexts, the luma and the
+// chroma residual contexts are pairwise disjoint, so the sum and every state are those of the interleaved syntax.  A tree without a level is not coded at all
+// (rqt_root_cbf = 0, itself not priced): rate 0, nothing moved.  The alternative form -- luma chain, chroma chain and flags on separate lanes, summed -- was not built.
+template <int L, int DEPTH>
+__global__ __launch_bounds__(64) void k_tree_rate(const int16_t *__restrict__ lumaLevels, const int16_t *__restrict__ chromaLevels, const uint8_t *__restrict__ states,
+                                                  const uint8_t *__restrict__ syntaxStates, const TreeRateJob *__restrict__ jobs, int njobs, int64_t *__restrict__ rates,
+                                                  uint32_t *__restrict__ cbfMasks, uint8_t *__restrict__ statesOut, uint8_t *__restrict__ syntaxOut)
+{
+    constexpr int LY = L - DEPTH, LC = (L == 3 ? 2 : L - 1 - DEPTH);      // the luma and chroma transform sizes of the depth
+    constexpr int NY = DEPTH ? 4 : 1, NC = (DEPTH && L > 3) ? 4 : 1;      // how many blocks of each
+    __shared__ IntraRateLds sh;
+    const int lane = threadIdx.x, first = blockIdx.x * 64, j = first + lane;
+    rateTables<LY>(sh.r, lane);
+    subBlockScan<LC>(sh.r, lane);
+    TreeRateJob job = TreeRateJob();
+    if (j < njobs) job = jobs[j];
+    // a job with a flag bit this kernel does not know is not walked: its rate becomes -1, its mask 0 and its snapshots pass through
+    const bool valid = j < njobs && (job.flags & ~HAVOC_TREE_RATE_SPLIT_FLAG_CODED) == 0;
+    sh.r.ctxIndex[lane] = j < njobs ? job.ctx_index : -1;
+    if (j < njobs)
+        for (int b = 0; b < HAVOC_INTRA_SYNTAX_CTX_BYTES; ++b) sh.syn[b][lane] = syntaxStates[(long)job.ctx_index * HAVOC_INTRA_SYNTAX_CTX_BYTES + b];
+    __syncthreads();
+    loadStates(sh.r, lane, states);
+    __syncthreads();
+    if (valid)
+    {
+        int64_t rate = 0;
+        uint32_t mask = 0;
+        bool coded;
+#pragma unroll 1
+        for (int k = 0; k < NY; ++k)
+        {
+            rate += walkBlock<LY>(sh.r, lane, lumaLevels + (long)job.luma_off + (long)k * (1 << 2 * LY), 0, 0, job.sdh, coded);
+            mask |= (uint32_t)coded << k;
+            if (NC == NY || k == NY - 1)
+            {
+                const int kc = NC == NY ? k : 0;
+                rate += walkBlock<LC>(sh.r, lane, chromaLevels + (long)job.cb_off + (long)kc * (1 << 2 * LC), 1, 0, job.sdh, coded);
+                mask |= (uint32_t)coded << (4 + kc);
+                rate += walkBlock<LC>(sh.r, lane, chromaLevels + (long)job.cr_off + (long)kc * (1 << 2 * LC), 2, 0, job.sdh, coded);
+                mask |= (uint32_t)coded << (8 + kc);
+            }
+        }
+        if (mask != 0)
+        {
+            const int cb = (mask & 0x0f0) != 0, cr = (mask & 0xf00) != 0;
+            if (job.flags & HAVOC_TREE_RATE_SPLIT_FLAG_CODED)
+            {
+                const int ctx = HAVOC_INTRA_SYNTAX_CTX_SPLIT_TRANSFORM_FLAG + 5 - L, e = sh.r.bins[2 * sh.syn[ctx][lane] + DEPTH];
+                sh.syn[ctx][lane] = (uint8_t)e;
+                rate += e >> 8;
+            }
+            rate += priceBin(sh.r, lane, HAVOC_RDOQ_CTX_CBF_CHROMA, cb);
+            rate += priceBin(sh.r, lane, HAVOC_RDOQ_CTX_CBF_CHROMA, cr);
+            if (DEPTH == 0)
+            {
+                if (cb || cr) rate += priceBin(sh.r, lane, HAVOC_RDOQ_CTX_CBF_LUMA + 1, (int)(mask & 1));
+            }
+            else
+                for (int k = 0; k < 4; ++k)
+                {
+                    if (NC == 4 && cb) rate += priceBin(sh.r, lane, HAVOC_RDOQ_CTX_CBF_CHROMA + 1, (int)(mask >> (4 + k)) & 1);
+                    if (NC == 4 && cr) rate += priceBin(sh.r, lane, HAVOC_RDOQ_CTX_CBF_CHROMA + 1, (int)(mask >> (8 + k)) & 1);
+                    rate += priceBin(sh.r, lane, HAVOC_RDOQ_CTX_CBF_LUMA, (int)(mask >> k) & 1);
+                }
+        }
+        rates[job.out_index] = rate;
+        cbfMasks[job.out_index] = mask;
+    }
+    else if (j < njobs)
+    {
+        rates[job.out_index] = -1;
+        cbfMasks[job.out_index] = 0;
+    }
+    if (syntaxOut != nullptr && j < njobs)
+        for (int b = 0; b < HAVOC_INTRA_SYNTAX_CTX_BYTES; ++b) syntaxOut[(long)j * HAVOC_INTRA_SYNTAX_CTX_BYTES + b] = sh.syn[b][lane];
+    if (statesOut == nullptr) return;
+    __syncthreads();
+    storeStates(sh.r, lane, first, njobs, statesOut);
+}
+
 } // namespace
+
+hipError_t launch_tree_rate(hipStream_t st, int log2Cb, int depth, const int16_t *lumaLevels, const int16_t *chromaLevels, const uint8_t *states, const uint8_t *syntaxStates,
+                            const TreeRateJob *j, int njobs, int64_t *rates, uint32_t *cbf, uint8_t *statesOut, uint8_t *syntaxOut)
+{
+    if (njobs <= 0) return hipSuccess;
+    const dim3 grid((njobs + 63) / 64), wg(64);
+#define TREE_RATE(L, D) hipLaunchKernelGGL((k_tree_rate<L, D>), grid, wg, 0, st, lumaLevels, chromaLevels, states, syntaxStates, j, njobs, rates, cbf, statesOut, syntaxOut)
+    if (log2Cb == 3 && depth == 0) TREE_RATE(3, 0);
+    else if (log2Cb == 3 && depth == 1) TREE_RATE(3, 1);
+    else if (log2Cb == 4 && depth == 0) TREE_RATE(4, 0);
+    else if (log2Cb == 4 && depth == 1) TREE_RATE(4, 1);
+    else if (log2Cb == 5 && depth == 0) TREE_RATE(5, 0);
+    else if (log2Cb == 5 && depth == 1) TREE_RATE(5, 1);
+    else return hipErrorInvalidValue;
+#undef TREE_RATE
+    return hipGetLastError();
+}
 
 hipError_t launch_intra_rate(hipStream_t st, int log2, const int16_t *levels, const uint8_t *states, const uint8_t *syntaxStates, const IntraRateJob *j, int njobs,
                              int64_t *rates, uint8_t *statesOut, uint8_t *syntaxOut)

@@ -47,6 +47,8 @@ hipError_t launch_rdoq(hipStream_t, int bd, int log2, int16_t *, const int16_t *
 hipError_t launch_rdoq_prescanned(hipStream_t, int bd, int log2, int16_t *, const int16_t *, const uint8_t *, const havoc_mi355x_rdoq_job *, int, int32_t *, void *);
 hipError_t launch_residual_rate(hipStream_t, int log2, const int16_t *, const uint8_t *, const havoc_mi355x_residual_rate_job *, int, int64_t *, uint8_t *);
 hipError_t launch_intra_rate(hipStream_t, int log2, const int16_t *, const uint8_t *, const uint8_t *, const havoc_mi355x_intra_rate_job *, int, int64_t *, uint8_t *, uint8_t *);
+hipError_t launch_tree_rate(hipStream_t, int log2Cb, int depth, const int16_t *, const int16_t *, const uint8_t *, const uint8_t *, const havoc_mi355x_tree_rate_job *, int, int64_t *,
+                            uint32_t *, uint8_t *, uint8_t *);
 hipError_t launch_intra_order(hipStream_t, const int32_t *, const havoc_mi355x_intra_mpm *, int, int32_t, int32_t *, int32_t *, int32_t *, int32_t *);
 hipError_t launch_intra_expand(hipStream_t, const havoc_mi355x_intra_search_job *, const int32_t *, const int32_t *, const int32_t *, const int32_t *, int, int, int, int, int,
                                int, int, int, havoc_mi355x_intra_job *, havoc_mi355x_tu_fused_job *, havoc_mi355x_rdoq_job *, int32_t *, int32_t *);
@@ -62,6 +64,9 @@ hipError_t launch_intra_commit(hipStream_t, int S, const havoc_mi355x_intra_chai
                                const int32_t *, int);
 hipError_t launch_rqt_decide(hipStream_t, const havoc_mi355x_rqt_unit *, int, const int32_t *, const int32_t *, const havoc_mi355x_rqt_size sizes[4], long, int, int, int32_t,
                              havoc_mi355x_rqt_choice *, const int64_t *const *rates);
+hipError_t launch_rqt_decide_tree(hipStream_t, const havoc_mi355x_rqt_unit *, int, const int32_t *, const int32_t *, const havoc_mi355x_rqt_size sizes[4],
+                                  const havoc_mi355x_rqt_size csizes[4], const havoc_mi355x_rqt_chroma_at *, const int64_t *, const uint32_t *, long, int, int, long, long, int, int,
+                                  int32_t, havoc_mi355x_rqt_choice *, havoc_mi355x_rqt_tree_choice *);
 hipError_t launch_block_cells(hipStream_t, int, int, int, int, const int16_t *, const havoc_mi355x_rqt_unit *, const havoc_mi355x_rqt_choice *, int, havoc_mi355x_cell *, bool);
 hipError_t launch_merge_decide(hipStream_t, const int32_t *, const int32_t *, const int32_t *, int, int64_t, int64_t *, int32_t *);
 hipError_t launch_merge_jobs(hipStream_t, const havoc_mi355x_field_layout *, const int16_t *, const int32_t *, const int32_t *, int, int, havoc_mi355x_pred_bi_job *,

@@ -454,14 +454,23 @@ class DecisionPicture:
     PAD = 96
 
     def __init__(self, hv, width, height, bit_depth=8, qp=32, seed=11, threads=16, frames=None, density=1.0, intra=True, search_on_device=True, distance=1,
-                 sao=False, residual_rates=False):
+                 sao=False, residual_rates=False, tree_rates=False):
         import torch
         if sao and not search_on_device:
             raise ValueError("sao=True needs the device route (search_on_device=True)")
         if residual_rates and not search_on_device:
             raise ValueError("residual_rates=True needs the device route (search_on_device=True)")
+        if tree_rates and not search_on_device:
+            raise ValueError("tree_rates=True needs the device route (search_on_device=True)")
+        if tree_rates and residual_rates:
+            raise ValueError("tree_rates=True prices the whole transform tree, residuals included: not together with residual_rates=True")
+        if tree_rates and sao:
+            raise ValueError("tree_rates=True together with sao=True is not built")
         # the transform-tree decision prices each candidate's residual with the reference's CABAC bits (havoc_mi355x_residual_rate) in place of the stand-in
         self.residual_rates = residual_rates
+        # ... or compares what the reference compares: the whole transform_tree's bits of both depths (havoc_mi355x_tree_rate) and the distortion of three planes
+        # (havoc_mi355x_rqt_decide_tree), luma AND chroma reconstructed at the decided depth
+        self.tree_rates = tree_rates
         self.sao = sao                                # in-loop SAO between deblocking and padding (sao_filter_inputs / sao_loop_filter)
         from . import havoc as hmod
         from . import workload
@@ -521,6 +530,10 @@ class DecisionPicture:
         base = srng.integers(4, 100, 128)
         self.rdoq_states = np.clip(base[None, :] + srng.integers(-6, 7, (self.cx * self.cy, 128)), 0, 125).astype(np.uint8)
         self.d_states = hv.up(self.rdoq_states.reshape(-1))
+        if tree_rates:      # the contexts outside the 128-byte snapshot (HAVOC_INTRA_SYNTAX_CTX_*: split_transform_flag's), per CTU, seeded the same way
+            yrng = np.random.default_rng(seed + 7927)
+            self.syntax_states = np.clip(yrng.integers(4, 100, 4)[None, :] + yrng.integers(-6, 7, (self.cx * self.cy, 4)), 0, 125).astype(np.uint8)
+            self.d_syntax_states = hv.up(self.syntax_states.reshape(-1))
         self.pred = hv.zeros(width * height, self.dt)
         self.recon = hv.zeros(self.pe, self.dt)
         # chroma (round 4): Cb / Cr of source, list 0, list 1 in ONE allocation (plane k at k * cpe: 0-2 Cb, 3-5 Cr), their prediction and reconstruction planes
@@ -673,6 +686,25 @@ class DecisionPicture:
         """the inter residual of the chroma planes at the decided vectors (turing/Reconstruct.cpp:1274-1286 with cIdx 1, 2): HavocPredUni 4-tap of every unit's
         Cb and Cr block at its list-0 vector (eighth-sample phase = the luma vector's low three bits), then residual + DCT -> Rdoq::runQuantisation (cIdx) ->
         de-quantise + inverse DCT + add -> SSD, one chain per chroma transform size, into the chroma reconstruction planes.  Asynchronous."""
+        hv, bd = self.hv, self.bd
+        hw = self.W // 2
+        self.chroma_predict()
+        for g in self.cgroups:
+            hv.tu_forward_d(bd, 0, g["log2"], g["coef"], self.d_cpic, self.cstride, self.cpred, hw, g["d_fj"])
+            hv.rdoq_d(bd, g["log2"], g["level"], g["coef"], self.d_states, g["d_rj"], g["cbf"], g["work"])
+            hv.tu_reconstruct_d(bd, 0, g["log2"], g["inv"], g["dshift"], self.crecon, self.cstride, self.cpred, hw, self.d_cpic, self.cstride, g["level"], g["d_fj"], g["ssd"])
+
+    def chroma_predict(self):
+        """the prediction half of chroma_chain alone: every unit's Cb and Cr block at its decided vector into cpred (tree_rates=True: the chroma candidates of both
+        depths are evaluated from it)"""
+        hv = self.hv
+        self._chroma_groups()
+        for g in self.cgroups:
+            hv.pred_jobs_d(self.layout, self.d_field, 0, g["d_x0"], g["d_y0"], g["log2"] + 1, g["comp"], g["d_dst"], g["d_pj"])
+            hv.pred_uni_d(4, self.bd, self.cpred, self.W // 2, self.d_cpic, self.cstride, g["d_pj"].view(-1, 8), g["cn"], g["cn"])
+
+    def _chroma_groups(self):
+        """chroma_chain's job tables and buffers per (unit size, component), built once"""
         hv, bd, torch, hmod = self.hv, self.bd, self.torch, self.hmod
         from . import workload
         u = self.units
@@ -705,12 +737,6 @@ class DecisionPicture:
                                              d_x0=hv.up(u["x0"][sel].astype(np.int32)), d_y0=hv.up(u["y0"][sel].astype(np.int32)), d_dst=hv.up(fj[:, 2]),
                                              d_pj=hv.zeros(m * 8, np.int32), coef=hv.zeros(m * cn * cn, np.int16),
                                              level=hv.zeros(m * cn * cn, np.int16), cbf=hv.zeros(m, np.int32), ssd=hv.zeros(m, np.uint32), work=hv.rdoq_workspace(m)))
-        for g in self.cgroups:
-            hv.pred_jobs_d(self.layout, self.d_field, 0, g["d_x0"], g["d_y0"], g["log2"] + 1, g["comp"], g["d_dst"], g["d_pj"])
-            hv.pred_uni_d(4, bd, self.cpred, hw, self.d_cpic, self.cstride, g["d_pj"].view(-1, 8), g["cn"], g["cn"])
-            hv.tu_forward_d(bd, 0, g["log2"], g["coef"], self.d_cpic, self.cstride, self.cpred, hw, g["d_fj"])
-            hv.rdoq_d(bd, g["log2"], g["level"], g["coef"], self.d_states, g["d_rj"], g["cbf"], g["work"])
-            hv.tu_reconstruct_d(bd, 0, g["log2"], g["inv"], g["dshift"], self.crecon, self.cstride, self.cpred, hw, self.d_cpic, self.cstride, g["level"], g["d_fj"], g["ssd"])
 
     def tu_chain(self, field, predicted=False):
         """prediction at the decided vectors, then the residual-quadtree decisions and the reconstruction; returns (decisions, stats)"""
@@ -782,8 +808,86 @@ class DecisionPicture:
         # a block-sized area nobody reads, inside the reconstruction's bottom border (rewritten by the padding that ends the step): where the candidates that lost go
         plan["dump"] = (self.H + self.PAD + 16) * self.stride + self.PAD
         plan["rl_q16"] = int((1.0 / self.lam) * 65536 + 0.5)
+        if self.tree_rates:
+            self._tree_plan(plan, zero_at, one_at)
         self._filter_buffers()
         return plan
+
+    def _tree_plan(self, plan, zero_at, one_at):
+        """tree_rates=True, beside the luma candidates of _rqt_plan: the chroma candidates of both depths per chroma transform size (a unit's depth-0 Cb and Cr block
+        of max(L - 1, 2); for L > 3 its four depth-1 Cb blocks, then its four Cr blocks, of L - 2, z-order; an 8x8 unit's one 4x4 block per component serves both
+        depths), where each unit finds them, and the tree_rate jobs per (unit size, depth) -- every tree from the unit's snapshot, out_index = 2 * unit + depth"""
+        hv, hmod, torch, bd = self.hv, self.hmod, self.torch, self.bd
+        from . import workload
+        u = self.units
+        hw, hh, c2 = self.W // 2, self.H // 2, self.PAD // 2
+        clists = {s: [] for s in (2, 3, 4)}
+        chroma_at = np.zeros(len(u), hmod.RQT_CHROMA_AT_DT)
+        for i in range(len(u)):
+            L = int(u["log2_size"][i])
+            c0 = max(L - 1, 2)
+            chroma_at[i]["cb_zero"], chroma_at[i]["cr_zero"] = len(clists[c0]), len(clists[c0]) + 1
+            clists[c0] += [(i, 0, 1, 0), (i, 0, 2, 0)]
+            if L > 3:
+                chroma_at[i]["cb_one"], chroma_at[i]["cr_one"] = len(clists[L - 2]), len(clists[L - 2]) + 4
+                clists[L - 2] += [(i, 1, comp, k) for comp in (1, 2) for k in range(4)]
+            else:
+                chroma_at[i]["cb_one"], chroma_at[i]["cr_one"] = chroma_at[i]["cb_zero"], chroma_at[i]["cr_zero"]
+        plan["chroma_at"], plan["d_chroma_at"] = chroma_at, hv.up(np.ascontiguousarray(chroma_at).view(np.int32))
+        plan["csizes"], plan["ctable"] = {}, np.zeros((4, 5), np.uint64)
+        for cl, cand in clists.items():
+            m = len(cand)
+            if not m:
+                continue
+            cn = 1 << cl
+            area = cn * cn
+            c = np.array(cand, np.int64)
+            x = u["x0"][c[:, 0]].astype(np.int64) // 2 + np.where(c[:, 1] == 1, (c[:, 3] & 1) * cn, 0)
+            y = u["y0"][c[:, 0]].astype(np.int64) // 2 + np.where(c[:, 1] == 1, (c[:, 3] >> 1) * cn, 0)
+            comp = c[:, 2]
+            jobs = np.stack([np.arange(m) * area, 3 * (comp - 1) * self.cpe + (y + c2) * self.cstride + x + c2, (comp - 1) * hw * hh + y * hw + x,
+                             np.arange(m) * area], 1).astype(np.int32)
+            qs, qshift, _ = workload.quant_params(self.qp, cl, bd, False)
+            inv, dshift = workload.dequant_params(self.qp, cl, bd)
+            rj = np.zeros(m, hmod.RDOQ_JOB_DT)
+            rj["dst_off"] = rj["src_off"] = jobs[:, 0]
+            rj["quant_scale"], rj["quant_shift"], rj["inv_scale"] = qs, qshift, inv
+            rj["lambda_q16"], rj["sdh_factor"] = hmod.rdoq_lambda(self.lam, inv)
+            rj["sdh"], rj["c_idx"] = 1, comp
+            rj["ctx_index"] = u["ctx_index"][c[:, 0]]
+            with torch.cuda.stream(hv.tstream):
+                d_rj = torch.from_numpy(rj.view(np.uint8).reshape(-1)).to(hv.device)
+            g = dict(log2=cl, nn=cn, m=m, inv=inv, dshift=dshift, cand=c, d_jobs=hv.up(jobs), d_fin=hv.zeros(m * 4, np.int32), d_rj=d_rj, coef=hv.zeros(m * area, np.int16),
+                     level=hv.zeros(m * area, np.int16), piece=hv.zeros(m * area, self.dt), work=hv.rdoq_workspace(m), cbf=hv.zeros(m, np.int32), ssd=hv.zeros(m, np.uint32),
+                     ssd2=hv.zeros(m, np.uint32))
+            plan["csizes"][cl] = g
+            plan["ctable"][cl - 2] = [g["cbf"].data_ptr(), g["ssd"].data_ptr(), 0, g["d_jobs"].data_ptr(), g["d_fin"].data_ptr()]
+            plan["launches"] += 4
+        plan["table"][:, 2] = 0          # (no level statistics on this route: nonzero / sum_abs of the results are 0)
+        plan["tree_jobs"] = {}
+        for L in (5, 4, 3):
+            sel = np.flatnonzero(u["log2_size"] == L)
+            if not len(sel):
+                continue
+            c0, c1 = max(L - 1, 2), max(L - 2, 2)
+            for depth in (0, 1):
+                tj = np.zeros(len(sel), hmod.TREE_RATE_JOB_DT)
+                if depth == 0:
+                    tj["luma_off"], tj["cb_off"], tj["cr_off"] = zero_at[sel] << 2 * L, chroma_at["cb_zero"][sel] << 2 * c0, chroma_at["cr_zero"][sel] << 2 * c0
+                else:
+                    tj["luma_off"], tj["cb_off"], tj["cr_off"] = one_at[sel] << 2 * (L - 1), chroma_at["cb_one"][sel] << 2 * c1, chroma_at["cr_one"][sel] << 2 * c1
+                tj["ctx_index"], tj["out_index"], tj["sdh"] = u["ctx_index"][sel], 2 * sel + depth, 1
+                tj["flags"] = hmod.TREE_RATE_SPLIT_FLAG_CODED      # MaxTrafoDepth 1, MinTbLog2SizeY 2, MaxTbLog2SizeY 5: coded for every unit of 8 .. 32
+                with torch.cuda.stream(hv.tstream):
+                    d_tj = torch.from_numpy(tj.view(np.uint8).reshape(-1).copy()).to(hv.device)
+                plan["tree_jobs"][L, depth] = dict(jobs=tj, d_jobs=d_tj, luma=L - depth, chroma=c1 if depth else c0)
+                plan["launches"] += 1
+        with torch.cuda.stream(hv.tstream):
+            plan["tree_rate"] = torch.zeros(2 * len(u), dtype=torch.int64, device=hv.device)
+        plan["tree_cbf"], plan["d_tree_out"] = hv.zeros(2 * len(u), np.int32), hv.zeros(4 * len(u), np.int32)
+        # where the chroma candidates that lost go: inside the chroma reconstruction's bottom border (nothing reads it)
+        plan["cdump"] = (hh + c2 + 8) * self.cstride + c2
+        plan["launches"] += 4 * len(np.unique(u["log2_size"])) - len(plan["sizes"])      # (chroma prediction: 2 per unit size and component; no level_stats)
 
     def _filter_buffers(self):
         """the block structure and the loop filter's edge data of the picture (one set per picture, whatever decides its units -- the whole-picture plan or the band views)"""
@@ -883,6 +987,8 @@ class DecisionPicture:
             self.rqt_plan = self._rqt_plan()
         P = self.rqt_plan
         src = self.d_pic
+        if self.tree_rates:
+            return self._tree_decisions_three_planes(P)
         for g in P["sizes"].values():
             hv.tu_forward_d(bd, 0, g["log2"], g["coef"], src, self.stride, self.pred, self.W, g["d_jobs"].view(-1, 4))
             hv.rdoq_d(bd, g["log2"], g["level"], g["coef"], self.d_states, g["d_rj"], g["cbf"], g["work"])
@@ -900,6 +1006,44 @@ class DecisionPicture:
             hv.tu_reconstruct_d(bd, 0, g["log2"], g["inv"], g["dshift"], self.recon, self.stride, self.pred, self.W, src, self.stride, g["level"], g["d_fin"].view(-1, 4), g["ssd2"])
         return P
 
+    def _tree_decisions_three_planes(self, P):
+        """tree_rates=True: chroma prediction; the luma candidates as on the default route; the chroma candidates of both depths per chroma size (residual + DCT ->
+        RDOQ with cIdx 1 / 2 from the unit's snapshot -> IQ + IDCT + add -> SSD, into pieces); the whole-tree rate and cbf mask per (unit size, depth); the decision
+        over three planes; every candidate reconstructed again -- the chosen trees' luma into recon AND chroma into crecon"""
+        hv, bd, src, hw = self.hv, self.bd, self.d_pic, self.W // 2
+        self.chroma_predict()
+        for g in P["sizes"].values():
+            hv.tu_forward_d(bd, 0, g["log2"], g["coef"], src, self.stride, self.pred, self.W, g["d_jobs"].view(-1, 4))
+            hv.rdoq_d(bd, g["log2"], g["level"], g["coef"], self.d_states, g["d_rj"], g["cbf"], g["work"])
+            hv.tu_reconstruct_d(bd, 0, g["log2"], g["inv"], g["dshift"], g["piece"], g["nn"], self.pred, self.W, src, self.stride, g["level"], g["d_jobs"].view(-1, 4), g["ssd"])
+        for g in P["csizes"].values():
+            hv.tu_forward_d(bd, 0, g["log2"], g["coef"], self.d_cpic, self.cstride, self.cpred, hw, g["d_jobs"].view(-1, 4))
+            hv.rdoq_d(bd, g["log2"], g["level"], g["coef"], self.d_states, g["d_rj"], g["cbf"], g["work"])
+            hv.tu_reconstruct_d(bd, 0, g["log2"], g["inv"], g["dshift"], g["piece"], g["nn"], self.cpred, hw, self.d_cpic, self.cstride, g["level"], g["d_jobs"].view(-1, 4),
+                                g["ssd"])
+        for (L, depth), t in P["tree_jobs"].items():
+            hv.tree_rate_d(L, depth, P["sizes"][t["luma"]]["level"], P["csizes"][t["chroma"]]["level"], self.d_states, self.d_syntax_states, t["d_jobs"], P["tree_rate"],
+                           P["tree_cbf"])
+        self._rqt_rates = self._rqt_tree = None
+        hv.rqt_decide_tree_d(P["d_units"].view(-1, 4), P["d_zero_at"], P["d_one_at"], P["table"], P["ctable"], P["d_chroma_at"], P["tree_rate"], P["tree_cbf"], self.origin,
+                             self.stride, P["dump"], self.corigin, self.cpe + self.corigin, self.cstride, P["cdump"], P["rl_q16"], P["d_out"], P["d_tree_out"])
+        for g in P["sizes"].values():
+            hv.tu_reconstruct_d(bd, 0, g["log2"], g["inv"], g["dshift"], self.recon, self.stride, self.pred, self.W, src, self.stride, g["level"], g["d_fin"].view(-1, 4), g["ssd2"])
+        for g in P["csizes"].values():
+            hv.tu_reconstruct_d(bd, 0, g["log2"], g["inv"], g["dshift"], self.crecon, self.cstride, self.cpred, hw, self.d_cpic, self.cstride, g["level"], g["d_fin"].view(-1, 4),
+                                g["ssd2"])
+        return P
+
+    @property
+    def rqt_tree_results(self):
+        """tree_rates=True: what the decision over three planes adds per unit (havoc.RQT_TREE_RESULT_DT: both cbf masks, both sums ssdCb + ssdCr): downloaded when
+        asked for"""
+        if not self.tree_rates:
+            raise ValueError("rqt_tree_results: the picture was made without tree_rates=True")
+        if getattr(self, "_rqt_tree", None) is None:
+            self._rqt_tree = self.hv.down(self.rqt_plan["d_tree_out"], np.int32).view(self.hmod.RQT_TREE_RESULT_DT).copy()
+        return self._rqt_tree
+
     @property
     def rqt_results(self):
         """the transform-tree decisions of the last step (RQT_RESULT_DT per unit): downloaded when asked for"""
@@ -915,8 +1059,14 @@ class DecisionPicture:
     def rqt_rates(self):
         """residual_rates=True: {log2: int64 Q16 rate of every candidate of that transform size} of the last step (the order of rqt_plan["sizes"][log2]'s jobs):
         downloaded when asked for"""
+        if self.tree_rates:      # ... tree_rates=True: {(unit size, depth): the whole-tree rate of every unit of that size, in the order of rqt_plan["tree_jobs"]}
+            if getattr(self, "_rqt_rates", None) is None:
+                with self.torch.cuda.stream(self.hv.tstream):
+                    flat = self.rqt_plan["tree_rate"].cpu().numpy()
+                self._rqt_rates = {key: flat[t["jobs"]["out_index"]].copy() for key, t in self.rqt_plan["tree_jobs"].items()}
+            return self._rqt_rates
         if not self.residual_rates:
-            raise ValueError("rqt_rates: the picture was made without residual_rates=True")
+            raise ValueError("rqt_rates: the picture was made without residual_rates=True or tree_rates=True")
         if getattr(self, "_rqt_rates", None) is None:
             self._rqt_rates = {log2: self.hv.down(g["rates"], np.int64).copy() for log2, g in self.rqt_plan["sizes"].items()}
         return self._rqt_rates
@@ -1033,10 +1183,12 @@ class DecisionPicture:
         if self.search_on_device:
             # everything after the searches is a FIXED sequence of launches over device-resident tables (the decided field never leaves the device, the decisions
             # between the launches are kernels): recorded once into a HIP graph, one launch per picture, one wait at the end
-            self._rqt = self._cells = self._sao_decisions = self._rqt_rates = None
+            self._rqt = self._cells = self._sao_decisions = self._rqt_rates = self._rqt_tree = None
             if self.sao:
                 self._replayed("after the searches", lambda: (self.merge_candidates(field), self.predict(field), self.sao_filter_inputs(field),
                                                               self.sao_loop_filter()))
+            elif self.tree_rates:      # (the chroma reconstruction is the tree decision's own: chroma_chain, which codes chroma at depth 0 always, does not run)
+                self._replayed("after the searches", lambda: (self.merge_candidates(field), self.predict(field), self.tree_and_filter_on_device()))
             else:
                 self._replayed("after the searches", lambda: (self.merge_candidates(field), self.predict(field), self.tree_and_filter_on_device(),
                                                               self.chroma_chain(field)))
@@ -1096,6 +1248,8 @@ class DecisionPicture:
             raise ValueError("step_banded needs the device search")
         if self.residual_rates:
             raise ValueError("step_banded does not price residuals with CABAC rates: use step() with residual_rates=True")
+        if self.tree_rates:
+            raise ValueError("step_banded does not price transform trees with CABAC rates: use step() with tree_rates=True")
         if self.sao:
             # SAO of band b reads the deblocked rows of band b + 1 (turing/TaskSao.cpp:46-56): not built
             raise ValueError("step_banded does not run SAO: use step() with sao=True")

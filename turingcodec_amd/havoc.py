@@ -130,8 +130,10 @@ def _load():
         "residual_rate": [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp],
         "intra_rate": [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp],
         "intra_rate_jobs": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
+        "tree_rate": [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp],
         "intra_decide_rated": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_int32, _vp, _vp],
         "rqt_decide_rated": [_vp, _vp, _i, _vp, _vp, _vp, _vp, C.c_int64, C.c_ssize_t, _i, _i, _vp],
+        "rqt_decide_tree": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_ssize_t, _i, C.c_int64, C.c_int64, C.c_ssize_t, _i, _i, _vp, _vp],
         "sao_stats": [_vp, _i, _i, _vp, _ip, _vp, _ip, _vp, _i, _vp],
         "sao_filter": [_vp, _i, _i, _vp, _ip, _vp, _ip, _vp, _i],
         "sao_band_chroma": [_vp, _i, _i, _vp, _ip, _vp, _ip, _vp, _i, _vp],
@@ -301,6 +303,15 @@ INTRA_RATE_JOB_DT = np.dtype([("level_off", "<i4"), ("ctx_index", "<i4"), ("rate
 assert INTRA_RATE_JOB_DT.itemsize == 32
 INTRA_RATE_SPLIT_FLAG_CODED, INTRA_RATE_DEPTH_NONZERO = 1, 2
 INTRA_SYNTAX_CTX_BYTES = 4      # HAVOC_INTRA_SYNTAX_CTX_*: prev_intra_luma_pred_flag, split_transform_flag[0..2]
+
+# one havoc_mi355x_tree_rate_job (include/havoc_mi355x.h), 32 bytes: one candidate transform tree of an inter unit at the launch's depth; flags: TREE_RATE_*
+TREE_RATE_JOB_DT = np.dtype([("luma_off", "<i4"), ("cb_off", "<i4"), ("cr_off", "<i4"), ("ctx_index", "<i4"), ("out_index", "<i4"), ("sdh", "u1"), ("flags", "u1"),
+                             ("pad", "u1", 2), ("reserved", "<i4", 2)])
+assert TREE_RATE_JOB_DT.itemsize == 32
+TREE_RATE_SPLIT_FLAG_CODED = 1
+# havoc_mi355x_rqt_chroma_at / havoc_mi355x_rqt_tree_choice (include/havoc_mi355x.h), 16 bytes each: where a unit's chroma candidates are / what rqt_decide_tree adds
+RQT_CHROMA_AT_DT = np.dtype([("cb_zero", "<i4"), ("cr_zero", "<i4"), ("cb_one", "<i4"), ("cr_one", "<i4")])
+RQT_TREE_RESULT_DT = np.dtype([("mask_zero", "<u4"), ("mask_one", "<u4"), ("chroma_ssd_zero", "<i4"), ("chroma_ssd_one", "<i4")])
 
 
 def rdoq_lambda(lam, inv_scale):
@@ -535,6 +546,15 @@ class Havoc:
         (residual_rate_d); the d_stats column of `sizes` may be 0"""
         self._ck(self.L.havoc_mi355x_rqt_decide_rated(self.h, _ptr(units), units.shape[0], _ptr(zero_at), _ptr(one_at), sizes.ctypes.data, rates.ctypes.data, int(rec_origin),
                                                       int(rec_stride), int(dump_off), int(rl_q16), _ptr(out)))
+
+    def rqt_decide_tree_d(self, units, zero_at, one_at, sizes, csizes, chroma_at, tree_rates, tree_cbf, rec_origin, rec_stride, dump_off, cb_origin, cr_origin, c_stride,
+                          c_dump_off, rl_q16, out, tree_out):
+        """the decision over three planes (havoc_mi355x_rqt_decide_tree): sizes / csizes = numpy uint64 [4, 5] of device addresses (luma / chroma candidate tables),
+        chroma_at: int32 tensor [n, 4] (RQT_CHROMA_AT_DT), tree_rates / tree_cbf: int64 / int32 tensors [2 n] as tree_rate_d writes them with out_index = 2 * unit +
+        depth; out: [n] havoc_mi355x_rqt_choice, tree_out: [n] RQT_TREE_RESULT_DT"""
+        self._ck(self.L.havoc_mi355x_rqt_decide_tree(self.h, _ptr(units), units.shape[0], _ptr(zero_at), _ptr(one_at), sizes.ctypes.data, csizes.ctypes.data, _ptr(chroma_at),
+                                                     _ptr(tree_rates), _ptr(tree_cbf), int(rec_origin), int(rec_stride), int(dump_off), int(cb_origin), int(cr_origin),
+                                                     int(c_stride), int(c_dump_off), int(rl_q16), _ptr(out), _ptr(tree_out)))
 
     def block_cells_add_d(self, width, height, qp, dpb_index0, field, units, decisions, cells):
         """the cells of `units` into cells that keep what they hold elsewhere (havoc_mi355x_block_cells_add)"""
@@ -903,6 +923,31 @@ class Havoc:
             after_sy = self.torch.zeros(max(len(jobs), 1) * INTRA_SYNTAX_CTX_BYTES, dtype=self.torch.uint8, device=self.device)
         self.intra_rate_d(log2, self.up(np.ascontiguousarray(levels, np.int16)), st, sy, j, rates, after, after_sy)
         return (self.down(rates, np.int64)[:nr], self.down(after, np.uint8)[:len(jobs) * 128].reshape(-1, 128),
+                self.down(after_sy, np.uint8)[:len(jobs) * INTRA_SYNTAX_CTX_BYTES].reshape(-1, INTRA_SYNTAX_CTX_BYTES))
+
+    def tree_rate_d(self, log2_cb, depth, luma_levels, chroma_levels, states, syntax_states, jobs, rates, cbf, states_out=None, syntax_states_out=None):
+        """the CABAC rate of an inter unit's whole transform tree at one depth: split_transform_flag, cbf_cb, cbf_cr, cbf_luma and the Y, Cb, Cr residual_coding
+        (havoc_mi355x_tree_rate); jobs: uint8 tensor holding TREE_RATE_JOB_DT records; rates: int64 tensor; cbf: int32 tensor (the masks); the two outputs: None, or
+        128 / 4 bytes per job.  No sync."""
+        self._ck(self.L.havoc_mi355x_tree_rate(self.h, log2_cb, depth, _ptr(luma_levels), _ptr(chroma_levels), _ptr(states), _ptr(syntax_states), _ptr(jobs),
+                                               jobs.numel() // TREE_RATE_JOB_DT.itemsize, _ptr(rates), _ptr(cbf), _ptr(states_out), _ptr(syntax_states_out)))
+
+    def tree_rate(self, log2_cb, depth, luma_levels, chroma_levels, states, syntax_states, jobs):
+        """numpy level: the levels int16, states uint8 [k, 128], syntax_states uint8 [k, 4], jobs TREE_RATE_JOB_DT array -> (rates int64 and masks uint32
+        [max out_index + 1], the entries no job writes 0; states_after uint8 [njobs, 128]; syntax_states_after uint8 [njobs, 4])"""
+        jobs = np.ascontiguousarray(jobs, TREE_RATE_JOB_DT)
+        nr = int(jobs["out_index"].max()) + 1 if len(jobs) else 0
+        with self.torch.cuda.stream(self.tstream):
+            st = self.torch.from_numpy(np.ascontiguousarray(states, np.uint8).reshape(-1)).to(self.device)
+            sy = self.torch.from_numpy(np.ascontiguousarray(syntax_states, np.uint8).reshape(-1)).to(self.device)
+            j = self.torch.from_numpy(jobs.view(np.uint8).reshape(-1).copy()).to(self.device)
+            rates = self.torch.zeros(max(nr, 1), dtype=self.torch.int64, device=self.device)
+            cbf = self.torch.zeros(max(nr, 1), dtype=self.torch.int32, device=self.device)
+            after = self.torch.zeros(max(len(jobs), 1) * 128, dtype=self.torch.uint8, device=self.device)
+            after_sy = self.torch.zeros(max(len(jobs), 1) * INTRA_SYNTAX_CTX_BYTES, dtype=self.torch.uint8, device=self.device)
+        self.tree_rate_d(log2_cb, depth, self.up(np.ascontiguousarray(luma_levels, np.int16)), self.up(np.ascontiguousarray(chroma_levels, np.int16)), st, sy, j, rates, cbf,
+                         after, after_sy)
+        return (self.down(rates, np.int64)[:nr], self.down(cbf, np.int32)[:nr].view(np.uint32), self.down(after, np.uint8)[:len(jobs) * 128].reshape(-1, 128),
                 self.down(after_sy, np.uint8)[:len(jobs) * INTRA_SYNTAX_CTX_BYTES].reshape(-1, INTRA_SYNTAX_CTX_BYTES))
 
     def intra_rate_jobs_d(self, mpm, order, count, slot, rdoq_jobs, n, flags, jobs):

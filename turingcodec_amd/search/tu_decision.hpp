@@ -13,7 +13,9 @@
 // measures residual_coding's CABAC bits per transform block on the device, bit for bit, and havoc_mi355x_rqt_decide_rated takes them in place of
 // `tuRate` (DecisionPicture(residual_rates=True)).  An INTRA candidate's whole rate can be the reference's too: havoc_mi355x_intra_rate measures what
 // EstimateRateLuma measures for it -- the mode bits in their CABAC state, split_transform_flag, cbf_luma, the residual -- and havoc_mi355x_intra_decide_rated /
-// havoc_search_intra_device_rated decide by it.  Still not priced for the inter tree: cbf_luma, split_transform_flag and its chroma residuals.
+// havoc_search_intra_device_rated decide by it.  The inter tree's WHOLE rate -- split_transform_flag, cbf_cb, cbf_cr, cbf_luma and the Y, Cb, Cr residuals with one
+// CABAC state -- is havoc_mi355x_tree_rate's, and havoc_mi355x_rqt_decide_tree (DecisionPicture(tree_rates=True)) decides by it over three planes.  Still not priced:
+// rqt_root_cbf, the prediction-unit and coding-unit bits, and contexts carried from unit to unit.
 // What is restated here -- and checked against the reference's tables + Rdoq.cpp -- is the
 // order of evaluation, the uncoded short-cut, the cost arithmetic (Q16) and the strict comparison.
 #pragma once
@@ -38,22 +40,36 @@ struct StandInTreeRate
     }
 };
 
+// the chroma side of a candidate tree: whether Cb or Cr has a level at that depth, and their SSDs.  The luma-only callers have none (the default); with
+// TreeChroma-like functors and the whole transform_tree's rate (havoc_mi355x_tree_rate) decideRqt is the reference's comparison over three planes, the
+// host form of havoc_mi355x_rqt_decide_tree
+struct ChromaOutcome { bool coded; int32_t ssd_cb, ssd_cr; };
+struct NoChroma
+{
+    ChromaOutcome operator()(int /*depth*/) const { return ChromaOutcome{false, 0, 0}; }
+};
+
 // View: havoc_tu_outcome evaluate(int x0, int y0, int log2, int depth) = the chain of Reconstruct.cpp:740-860 for the block at (x0, y0)
-template <class View, class Rate = StandInTreeRate>
-havoc_rqt_result decideRqt(View &view, const havoc_rqt_cu &cu, Lambda reciprocalLambda, Rate rate = Rate())
+// Chroma: ChromaOutcome operator()(int depth); the distortion of a depth is ssdY + 4 ssdCb + 4 ssdCr in int32 (StateEncodeSubstream::ssd), and a depth is
+// coded -- rqt_root_cbf -- when any of the three planes has a level
+template <class View, class Rate = StandInTreeRate, class Chroma = NoChroma>
+havoc_rqt_result decideRqt(View &view, const havoc_rqt_cu &cu, Lambda reciprocalLambda, Rate rate = Rate(), Chroma chroma = Chroma())
 {
     havoc_rqt_result r;
     r = havoc_rqt_result();
     const int half = 1 << (cu.log2_size - 1);
-    int32_t ssdOne = 0;
+    uint32_t ssdOne = 0;
     bool coded = false;
     for (int k = 0; k < 4; ++k)      // rqtdepth = 1 first (Reconstruct.cpp:1325-1326), blocks in z-order
     {
         r.one[k] = view.evaluate(cu.x0 + (k & 1) * half, cu.y0 + (k >> 1) * half, cu.log2_size - 1, 1);
-        ssdOne += int32_t(r.one[k].ssd);
+        ssdOne += r.one[k].ssd;
         coded |= r.one[k].cbf != 0;
     }
-    r.cost_one = rate(1, r.one, 4) + reciprocalLambda * ssdOne;
+    const ChromaOutcome c1 = chroma(1);
+    ssdOne += 4u * uint32_t(c1.ssd_cb) + 4u * uint32_t(c1.ssd_cr);
+    coded |= c1.coded;
+    r.cost_one = rate(1, r.one, 4) + reciprocalLambda * int32_t(ssdOne);
     if (!coded)                      // cbfZero: the unit is left unsplit and without residual
     {
         r.depth = 0;
@@ -62,7 +78,9 @@ havoc_rqt_result decideRqt(View &view, const havoc_rqt_cu &cu, Lambda reciprocal
     }
     r.tried_zero = 1;
     r.zero = view.evaluate(cu.x0, cu.y0, cu.log2_size, 0);
-    r.cost_zero = rate(0, &r.zero, 1) + reciprocalLambda * int32_t(r.zero.ssd);
+    const ChromaOutcome c0 = chroma(0);
+    const uint32_t ssdZero = r.zero.ssd + 4u * uint32_t(c0.ssd_cb) + 4u * uint32_t(c0.ssd_cr);
+    r.cost_zero = rate(0, &r.zero, 1) + reciprocalLambda * int32_t(ssdZero);
     r.depth = (r.cost_zero < r.cost_one) ? 0 : 1;     // Reconstruct.cpp:1389
     return r;
 }
