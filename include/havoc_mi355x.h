@@ -767,6 +767,83 @@ int havoc_mi355x_tree_rate(havoc_mi355x_ctx *ctx, int log2CbSize, int depth, con
                            const uint8_t *d_syntax_states, const havoc_mi355x_tree_rate_job *d_jobs, int njobs, int64_t *d_rate, uint32_t *d_cbf,
                            uint8_t *d_states_out, uint8_t *d_syntax_states_out);
 
+/* ---- the CABAC rate of a prediction unit's candidates and the inter mode decision (csrc/kernels_pu_rate.hip: k_pu_rate, k_pu_decide) ----
+ * What measurePuCost measures for every candidate go2 tries for a prediction unit (turing/Search.hpp:1656-1706, 1844-1902): Syntax<prediction_unit>
+ * (turing/SyntaxCtu.hpp:267-314) under Measure<void> from the contexts the unit started with.  One job = one candidate; in the syntax's order
+ *   - HAVOC_PU_RATE_SKIP (cu_skip_flag): only merge_idx, when MaxNumMergeCand > 1;
+ *   - else merge_flag, one context (turing/Binarization.h:538-547); HAVOC_PU_RATE_MERGE: merge_idx when MaxNumMergeCand > 1 -- truncated Rice with cMax =
+ *     MaxNumMergeCand - 1, bin 0 context-coded, the others bypass (:549-582);
+ *   - not merged: inter_pred_idc in B slices only (:585-612): with nPbW + nPbH != 12 bi is one bin 1 at ctxInc cqt_depth, uni is 0 there and then the list at ctxInc 4;
+ *     with nPbW + nPbH == 12 only the list bin at ctxInc 4.  Then for list 0 unless pred is L1, and for list 1 unless pred is L0: ref_idx_lX when
+ *     num_ref_idx_lX_active_minus1 > 0; mvd_coding (SyntaxCtu.hpp:382-405: greater0(x), greater0(y), greater1(x), greater1(y), then per component abs_mvd_minus2 --
+ *     EG1, bypass -- and the sign, bypass; Binarization.h:745-809), skipped for list 1 when mvd_l1_zero_flag is set and pred is BI; mvp_lX_flag (:811-831).
+ * ref_idx_l0 / ref_idx_l1 share two contexts, the two abs_mvd_greater0_flag bins one, the two abs_mvd_greater1_flag bins one, mvp_l0_flag / mvp_l1_flag one
+ * (turing/Cabac.h:112-126), so every bin is priced from the state the previous bins left.  ref_idx_lX: the reference has NO writer for it (its generic writer,
+ * Binarization.h:52-59, asserts in a debug build and writes nothing in a release one; its encoder searches refIdx 0 of lists of one picture, Search.hpp:1883-1884).
+ * It is priced here for every value the syntax allows as the inverse of the reference's reader (ReadRefIdx, turing/Read.h:1864-1888; H.265 9.3.4.2): truncated Rice with
+ * cMax = num_ref_idx_lX_active_minus1, bins 0 and 1 context-coded with ctxInc = binIdx, the rest bypass.  With num_ref_idx_lX_active_minus1 == 0 -- all the reference
+ * encoder produces -- every bit is the reference's own.
+ * Context-coded bins cost the Q15 table entry shifted to Q16 and move their context (measureEncodeDecision, turing/Write.h:476-506), bypass bins 1 << 16 (:559-567).
+ * These contexts are in neither the 128-byte snapshot nor the 4-byte intra one: d_syntax_states holds HAVOC_PU_SYNTAX_CTX_BYTES per snapshot, each byte a
+ * ContextModel::state, indexed by the job's ctx_index: */
+enum {
+    HAVOC_PU_SYNTAX_CTX_MERGE_FLAG = 0,         /* merge_flag [1] */
+    HAVOC_PU_SYNTAX_CTX_MERGE_IDX = 1,          /* merge_idx [1] */
+    HAVOC_PU_SYNTAX_CTX_INTER_PRED_IDC = 2,     /* inter_pred_idc [5]: ctxInc cqtDepth 0..3, 4 = the list bin */
+    HAVOC_PU_SYNTAX_CTX_REF_IDX = 7,            /* ref_idx_lX [2] */
+    HAVOC_PU_SYNTAX_CTX_ABS_MVD_GREATER0 = 9,   /* abs_mvd_greater0_flag [1] */
+    HAVOC_PU_SYNTAX_CTX_ABS_MVD_GREATER1 = 10,  /* abs_mvd_greater1_flag [1] */
+    HAVOC_PU_SYNTAX_CTX_MVP_FLAG = 11,          /* mvp_lX_flag [1] */
+    HAVOC_PU_SYNTAX_CTX_BYTES = 16              /* 12..15 reserved: passed through */
+};
+enum {
+    HAVOC_PU_RATE_MERGE = 1,   /* merge_flag = 1 */
+    HAVOC_PU_RATE_SKIP = 2     /* cu_skip_flag = 1 (merge_flag is not coded; HAVOC_PU_RATE_MERGE beside it changes nothing) */
+};
+enum { HAVOC_PU_PRED_L0 = 0, HAVOC_PU_PRED_L1 = 1, HAVOC_PU_PRED_BI = 2 };   /* = PRED_L0, PRED_L1, PRED_BI */
+typedef struct {
+    int32_t ctx_index;       /* the snapshot of d_syntax_states (16 bytes) the candidate starts from */
+    int32_t out_index;       /* the candidate's rate -> d_rate[out_index] */
+    int16_t mvd[2][2];       /* [list][x, y]: the motion vector difference, quarter samples; read for the lists `pred` uses */
+    uint8_t merge_idx;       /* read when merged or skipped */
+    uint8_t pred;            /* HAVOC_PU_PRED_*: inter_pred_idc; read when not merged */
+    uint8_t mvp_flag[2];     /* mvp_l0_flag, mvp_l1_flag */
+    uint8_t ref_idx[2];      /* ref_idx_l0, ref_idx_l1 */
+    uint8_t w, h;            /* nPbW, nPbH: only w + h == 12 (8x4 / 4x8) is looked at */
+    uint8_t cqt_depth;       /* cqtDepth of the coding quadtree the unit belongs to, 0..3 */
+    uint8_t flags;           /* HAVOC_PU_RATE_* */
+    uint8_t pad[2];
+    int32_t reserved;
+} havoc_mi355x_pu_rate_job;   /* sizeof: 32 */
+typedef struct {
+    int32_t slice_b;                        /* slice_type == B (else P: inter_pred_idc is not coded) */
+    int32_t max_num_merge_cand;             /* MaxNumMergeCand, 1..5 */
+    int32_t mvd_l1_zero_flag;
+    int32_t num_ref_idx_active_minus1[2];   /* num_ref_idx_l0_active_minus1, num_ref_idx_l1_active_minus1, 0..15 */
+    int32_t reserved[3];
+} havoc_mi355x_pu_slice;   /* sizeof: 32; read on the host at the call, passed by value */
+/* A job the syntax cannot code is not walked: d_rate[out_index] = -1 and its output snapshot is its input snapshot.  That is: a `flags` bit other than HAVOC_PU_RATE_*;
+ * merged or skipped with merge_idx >= MaxNumMergeCand; not merged with pred > 2, with pred BI and w + h == 12, with pred other than L0 in a P slice, with cqt_depth > 3
+ * (it indexes the contexts), or -- for a list pred uses -- mvp_flag > 1 or ref_idx > num_ref_idx_lX_active_minus1.  ctx_index and out_index are trusted; w and h are
+ * trusted (whether a unit of that shape exists is the caller's).  d_syntax_states is never written.  d_syntax_out: NULL, or njobs x 16 bytes: the snapshot as candidate j
+ * left it.  All device pointers 8-byte aligned.  EINVAL: a null d_syntax_states, d_jobs, slice or d_rate; njobs < 0; MaxNumMergeCand outside 1..5;
+ * num_ref_idx_lX_active_minus1 outside 0..15; d_syntax_out == d_syntax_states.  No allocation, no synchronisation, no workspace: capturable into a HIP graph. */
+int havoc_mi355x_pu_rate(havoc_mi355x_ctx *ctx, const uint8_t *d_syntax_states, const havoc_mi355x_pu_rate_job *d_jobs, int njobs, const havoc_mi355x_pu_slice *slice,
+                         int64_t *d_rate, uint8_t *d_syntax_out);
+/* go2's comparison (turing/Search.hpp:1829-1842) of n prediction units, a lane per unit.  Unit i's candidates are the contiguous entries [d_first[i], d_first[i] +
+ * d_count[i]) of d_rate (havoc_mi355x_pu_rate with out_index = job index), d_satd_y / _cb / _cr and d_syntax_after (havoc_mi355x_pu_rate's d_syntax_out), in the order the
+ * reference tries them: merge 0..N-1 for units that are not 2Nx2N, then L0, L1, BI.  WHICH candidates exist is the caller's (L0 / L1 only when that list has a
+ * reference; BI only when both uni candidates exist and nPbW + nPbH != 12, Search.hpp:1883-1891).  d_cost[t] = d_rate[t] + int64(int32(satdY + satdCb + satdCr)) *
+ * reciprocal_sqrt_lambda_q16 (measurePuCost, :1705; FixedPoint<int32_t, 16> * int32_t, turing/FixedPoint.h:79; the lambda is Lambda::set(double): int32(d * 65536 + 0.5)),
+ * or -1 for a candidate whose rate is -1, which is never chosen.  d_best[i]: the first of the cheapest, as an index within the unit (a later candidate replaces the best
+ * only when cost < bestCost), or -1 when the unit has no valid candidate; d_best_cost[i]: its cost, or -1.  d_best_syntax: NULL, or n x 16 bytes: the winner's snapshot
+ * from d_syntax_after (bestContextsAndCost), 16 zero bytes for a unit without a winner.  d_first and d_count are trusted.  The inputs are never written.  d_rate, d_cost,
+ * d_best_cost, d_syntax_after and d_best_syntax 8-byte aligned.  EINVAL: a null pointer other than d_syntax_after / d_best_syntax, d_best_syntax without d_syntax_after,
+ * n < 0, a negative lambda, an output that is one of the inputs.  No allocation, no synchronisation, no workspace: capturable into a HIP graph. */
+int havoc_mi355x_pu_decide(havoc_mi355x_ctx *ctx, const int32_t *d_first, const int32_t *d_count, int n, const int64_t *d_rate, const int32_t *d_satd_y,
+                           const int32_t *d_satd_cb, const int32_t *d_satd_cr, int32_t reciprocal_sqrt_lambda_q16, const uint8_t *d_syntax_after, int64_t *d_cost,
+                           int32_t *d_best, int64_t *d_best_cost, uint8_t *d_best_syntax);
+
 /* The same two steps with the scan of the coefficients done where they are produced (16x16 / 32x32 blocks; round 3):
  *   tu_forward_scan  = tu_forward + the first pass of the device RDOQ (which 4x4 groups hold a rounded level, the block's energy -> d_work;
  *                      the level block of d_rdoq_jobs[i].dst_off zeroed).  d_rdoq_jobs[i] describes the same block as d_jobs[i]

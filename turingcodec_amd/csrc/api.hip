@@ -27,6 +27,8 @@ static_assert(offsetof(havoc_mi355x_sao_params, dist_sao) == 88 && offsetof(havo
 static_assert(sizeof(havoc_mi355x_sao_decision) == 128 && offsetof(havoc_mi355x_sao_decision, merge_left) == 88 &&
               offsetof(havoc_mi355x_sao_decision, ctx_merge_before) == 104 && offsetof(havoc_mi355x_sao_decision, decided) == 108, "sao record ABI");
 static_assert(sizeof(havoc_mi355x_residual_rate_job) == 32 && offsetof(havoc_mi355x_residual_rate_job, c_idx) == 12, "job ABI");
+static_assert(sizeof(havoc_mi355x_pu_rate_job) == 32 && offsetof(havoc_mi355x_pu_rate_job, mvd) == 8 && offsetof(havoc_mi355x_pu_rate_job, flags) == 25 &&
+              sizeof(havoc_mi355x_pu_slice) == 32, "the prediction-unit rate records are ABI");
 static_assert(sizeof(havoc_mi355x_intra_rate_job) == 32 && offsetof(havoc_mi355x_intra_rate_job, scan_idx) == 12 && offsetof(havoc_mi355x_intra_rate_job, flags) == 15,
               "job ABI");
 static_assert(sizeof(havoc_mi355x_tree_rate_job) == 32 && offsetof(havoc_mi355x_tree_rate_job, out_index) == 16 && offsetof(havoc_mi355x_tree_rate_job, flags) == 21, "job ABI");
@@ -1085,6 +1087,36 @@ int havoc_mi355x_tree_rate(havoc_mi355x_ctx *ctx, int log2CbSize, int depth, con
     REQUIRE(d_syntax_states_out != d_syntax_states, "tree_rate: d_syntax_states_out must not be d_syntax_states (which is never written)");
     return check(launch_tree_rate(LS(ctx), log2CbSize, depth, d_luma_levels, d_chroma_levels, d_states, d_syntax_states, d_jobs, njobs, d_rate, d_cbf, d_states_out,
                                   d_syntax_states_out), "tree_rate");
+}
+
+int havoc_mi355x_pu_rate(havoc_mi355x_ctx *ctx, const uint8_t *d_syntax_states, const havoc_mi355x_pu_rate_job *d_jobs, int njobs, const havoc_mi355x_pu_slice *slice,
+                         int64_t *d_rate, uint8_t *d_syntax_out)
+{
+    REQUIRE_CTX(); REQUIRE(njobs >= 0, "njobs < 0");
+    REQUIRE(d_syntax_states && d_jobs && slice && d_rate, "pu_rate: null pointer");
+    REQUIRE(slice->max_num_merge_cand >= 1 && slice->max_num_merge_cand <= 5, "pu_rate: MaxNumMergeCand must be 1..5");
+    REQUIRE(slice->num_ref_idx_active_minus1[0] >= 0 && slice->num_ref_idx_active_minus1[0] <= 15 && slice->num_ref_idx_active_minus1[1] >= 0 &&
+            slice->num_ref_idx_active_minus1[1] <= 15, "pu_rate: num_ref_idx_lX_active_minus1 must be 0..15");
+    REQUIRE(((reinterpret_cast<uintptr_t>(d_syntax_states) | reinterpret_cast<uintptr_t>(d_rate) | reinterpret_cast<uintptr_t>(d_syntax_out) |
+              reinterpret_cast<uintptr_t>(d_jobs)) & 7) == 0, "pu_rate: d_syntax_states, d_jobs, d_rate and d_syntax_out must be 8-byte aligned");
+    REQUIRE(d_syntax_out != d_syntax_states, "pu_rate: d_syntax_out must not be d_syntax_states (which is never written)");
+    return check(launch_pu_rate(LS(ctx), d_syntax_states, d_jobs, njobs, slice, d_rate, d_syntax_out), "pu_rate");
+}
+
+int havoc_mi355x_pu_decide(havoc_mi355x_ctx *ctx, const int32_t *d_first, const int32_t *d_count, int n, const int64_t *d_rate, const int32_t *d_satd_y,
+                           const int32_t *d_satd_cb, const int32_t *d_satd_cr, int32_t reciprocal_sqrt_lambda_q16, const uint8_t *d_syntax_after, int64_t *d_cost,
+                           int32_t *d_best, int64_t *d_best_cost, uint8_t *d_best_syntax)
+{
+    REQUIRE_CTX(); REQUIRE(n >= 0, "n < 0"); REQUIRE(reciprocal_sqrt_lambda_q16 >= 0, "reciprocal_sqrt_lambda_q16 < 0");
+    REQUIRE(d_first && d_count && d_rate && d_satd_y && d_satd_cb && d_satd_cr && d_cost && d_best && d_best_cost, "pu_decide: null device pointer");
+    REQUIRE(d_best_syntax == nullptr || d_syntax_after != nullptr, "pu_decide: d_best_syntax needs d_syntax_after");
+    REQUIRE(d_best_syntax == nullptr || d_best_syntax != d_syntax_after, "pu_decide: d_best_syntax must not be d_syntax_after (which is never written)");
+    REQUIRE(d_cost != d_rate && d_best_cost != d_rate, "pu_decide: d_cost and d_best_cost must not be d_rate (which is never written)");
+    REQUIRE(((reinterpret_cast<uintptr_t>(d_rate) | reinterpret_cast<uintptr_t>(d_cost) | reinterpret_cast<uintptr_t>(d_best_cost) |
+              reinterpret_cast<uintptr_t>(d_syntax_after) | reinterpret_cast<uintptr_t>(d_best_syntax)) & 7) == 0,
+            "pu_decide: d_rate, d_cost, d_best_cost, d_syntax_after and d_best_syntax must be 8-byte aligned");
+    return check(launch_pu_decide(LS(ctx), d_first, d_count, n, d_rate, d_satd_y, d_satd_cb, d_satd_cr, reciprocal_sqrt_lambda_q16, d_syntax_after, d_cost, d_best,
+                                  d_best_cost, d_best_syntax), "pu_decide");
 }
 
 } // extern "C"

@@ -449,13 +449,23 @@ class DecisionPicture:
          reconstruction that the encoder has (stated; that chain needs a device-side loop).
 
     What is NOT in it (stated, not hidden): the encoder's mode decision between the searched PUs (every PU of workload.picture_pus is
-    searched and the last one covering an area stands) and between inter and intra, bi-prediction, CABAC.  `step()` is what bench.py times."""
+    searched and the last one covering an area stands) and between inter and intra, bi-prediction, CABAC.  `step()` is what bench.py times.
+
+    pu_modes=True (device route only) adds the decision WITHIN every searched prediction unit that go2 takes (turing/Search.hpp:1844-1902): its uni L0, uni L1 and
+    bi candidates -- the search's own records: the two uni-directional results and the two bi-directional refinements, list l's refined record holding what
+    searchMotionBi leaves in codedPu for list l -- predicted in three planes, measured with the SATD against the source, priced with the reference's CABAC bits
+    (havoc_mi355x_pu_rate) from one 16-byte snapshot per CTU and compared (havoc_mi355x_pu_decide), inside the replayed graph; `pu_decisions` has the outcome.  The
+    workload's units are 2Nx2N of 64 to 8, so go2 tries no merge candidate and every unit may be bi.  Still out: writing the winner's prediction into `pred` / `cpred`
+    (overlapping searched units make that a coding-unit decision: predict() keeps the list-0 vector), the merge candidates of searchMerge2Nx2N, contexts carried from
+    unit to unit, the coding-unit bits, and the search walk's predictors taking decided modes."""
 
     PAD = 96
 
     def __init__(self, hv, width, height, bit_depth=8, qp=32, seed=11, threads=16, frames=None, density=1.0, intra=True, search_on_device=True, distance=1,
-                 sao=False, residual_rates=False, tree_rates=False):
+                 sao=False, residual_rates=False, tree_rates=False, pu_modes=False):
         import torch
+        if pu_modes and not search_on_device:
+            raise ValueError("pu_modes=True needs the device route (search_on_device=True)")
         if sao and not search_on_device:
             raise ValueError("sao=True needs the device route (search_on_device=True)")
         if residual_rates and not search_on_device:
@@ -471,6 +481,8 @@ class DecisionPicture:
         # ... or compares what the reference compares: the whole transform_tree's bits of both depths (havoc_mi355x_tree_rate) and the distortion of three planes
         # (havoc_mi355x_rqt_decide_tree), luma AND chroma reconstructed at the decided depth
         self.tree_rates = tree_rates
+        # every searched prediction unit's inter mode (L0 / L1 / bi) by the reference's CABAC bits and three-plane SATDs (havoc_mi355x_pu_rate / _pu_decide)
+        self.pu_modes = pu_modes
         self.sao = sao                                # in-loop SAO between deblocking and padding (sao_filter_inputs / sao_loop_filter)
         from . import havoc as hmod
         from . import workload
@@ -534,6 +546,11 @@ class DecisionPicture:
             yrng = np.random.default_rng(seed + 7927)
             self.syntax_states = np.clip(yrng.integers(4, 100, 4)[None, :] + yrng.integers(-6, 7, (self.cx * self.cy, 4)), 0, 125).astype(np.uint8)
             self.d_syntax_states = hv.up(self.syntax_states.reshape(-1))
+        if pu_modes:        # prediction_unit()'s contexts (HAVOC_PU_SYNTAX_CTX_*), per CTU, seeded the same way
+            prng = np.random.default_rng(seed + 7933)
+            self.pu_syntax_states = np.clip(prng.integers(4, 100, hmod.PU_SYNTAX_CTX_BYTES)[None, :] +
+                                            prng.integers(-6, 7, (self.cx * self.cy, hmod.PU_SYNTAX_CTX_BYTES)), 0, 125).astype(np.uint8)
+            self.d_pu_syntax_states = hv.up(self.pu_syntax_states.reshape(-1))
         self.pred = hv.zeros(width * height, self.dt)
         self.recon = hv.zeros(self.pe, self.dt)
         # chroma (round 4): Cb / Cr of source, list 0, list 1 in ONE allocation (plane k at k * cpe: 0-2 Cb, 3-5 Cr), their prediction and reconstruction planes
@@ -681,6 +698,138 @@ class DecisionPicture:
                 best[g["sel"]] = hv.down(g["d_best"], np.int32)
             self._merge = dict(vectors=vec, satd=satd, cost=cost, best=best)
         return self._merge
+
+    # ---- the inter mode of every searched prediction unit (go2, turing/Search.hpp:1844-1902) ---------------------------------------------------------
+    PU_CANDIDATES = 3       # L0, L1, bi: the order go2 tries them in for a 2Nx2N unit
+
+    def _pu_plan(self):
+        """pu_modes' job tables and buffers, built once.  The units of one size form a group (a prediction block is then a contiguous size x size block of its
+        group's buffer); candidate 3 i + k of the group's i-th unit (k: 0 L0, 1 L1, 2 bi) has the global index at + 3 i + k, which names its rate, SATDs, cost and
+        snapshot; unit p's candidates start at first[p]."""
+        if hasattr(self, "pu_plan"):
+            return self.pu_plan
+        hv, torch, hmod, K = self.hv, self.torch, self.hmod, self.PU_CANDIDATES
+        pus, n = self.pus, len(self.pus)
+        if not ((pus["w"] == pus["h"]) & (pus["part_2Nx2N"] == 1) & (pus["w"] >= 8)).all():
+            raise ValueError("pu_modes=True handles 2Nx2N units of 64 to 8 (no merge candidate in go2, bi allowed)")
+        M = K * n
+        first, groups, at = np.zeros(n, np.int32), [], 0
+        for log2 in (6, 5, 4, 3):
+            sel = np.flatnonzero(pus["w"] == 1 << log2)
+            if not len(sel):
+                continue
+            nn, m = 1 << log2, K * len(sel)
+            first[sel] = at + K * np.arange(len(sel))
+            x0, y0 = pus["x0"][sel].astype(np.int64), pus["y0"][sel].astype(np.int64)
+            g = dict(log2=log2, nn=nn, sel=sel, m=m, at=at, x0=x0, y0=y0, planes=[])
+            for plane in range(3):
+                c = plane > 0
+                size, stride, pad, pe = (nn // 2, self.cstride, self.PAD // 2, self.cpe) if c else (nn, self.stride, self.PAD, self.pe)
+                bx, by = (x0 // 2, y0 // 2) if c else (x0, y0)
+                src = (3 * (plane - 1)) if c else 0                   # plane index of the source inside the allocation (Cb: 0, Cr: 3; luma: 0)
+                here = (by + pad) * stride + bx + pad
+                dst = np.arange(m) * size * size
+                sj = np.stack([src * pe + np.repeat(here, K), dst, np.full(m, size), np.full(m, size)], 1).astype(np.int32)
+                g["planes"].append(dict(size=size, stride=stride, taps=4 if c else 8, shift=3 if c else 2, here=here, first_ref=src + 1, pe=pe,
+                                        d_uj=hv.zeros(2 * len(sel) * 8, np.int32), d_bj=hv.zeros(len(sel) * 12, np.int32), d_sj=hv.up(sj),
+                                        d_dst=hv.zeros(m * size * size, self.dt)))
+            groups.append(g)
+            at += m
+        jobs = np.zeros(M, hmod.PU_RATE_JOB_DT)
+        ctu = ((pus["y0"] // 64) * self.cx + pus["x0"] // 64).astype(np.int32)
+        for k in range(K):
+            at_k = first + k
+            jobs["ctx_index"][at_k], jobs["pred"][at_k] = ctu, k
+            jobs["w"][at_k], jobs["h"][at_k], jobs["cqt_depth"][at_k] = pus["w"], pus["h"], pus["cqt_depth"]
+        jobs["out_index"] = np.arange(M)
+        with torch.cuda.stream(hv.tstream):
+            i64 = lambda count: torch.zeros(count, dtype=torch.int64, device=hv.device)
+            self.pu_plan = dict(groups=groups, first=first, jobs=jobs, M=M, d_first=hv.up(first), d_count=hv.up(np.full(n, K, np.int32)),
+                                d_jobs=torch.zeros(M * hmod.PU_RATE_JOB_DT.itemsize, dtype=torch.uint8, device=hv.device), d_satd=hv.zeros(3 * M, np.int32),
+                                d_rate=i64(M), d_cost=i64(M), d_best=hv.zeros(n, np.int32), d_best_cost=i64(n),
+                                d_after=hv.zeros(M * hmod.PU_SYNTAX_CTX_BYTES, np.uint8), d_best_syntax=hv.zeros(n * hmod.PU_SYNTAX_CTX_BYTES, np.uint8),
+                                slice=hmod.PuSlice(slice_b=1, max_num_merge_cand=5, mvd_l1_zero_flag=0, num_ref_idx_active_minus1=(0, 0)))
+        return self.pu_plan
+
+    def pu_candidates(self, res):
+        """the candidate and job tables of pu_modes from the search's records, on the host (they arrive there when search() returns), uploaded into the persistent
+        buffers the replayed launches read: res[2 p + l] the uni-directional result of unit p in list l, self.bi_results[2 p + l] list l's bi-directional refinement.
+        L0 / L1: mv, mvd, mvp_flag of the uni record; bi: list l's mv, mvd, mvp_flag of list l's refined record (what searchMotionBi leaves in codedPu,
+        turing/Search.hpp:1651-1652, 1817-1822).  refIdx is 0 (Search.hpp:1883-1884)."""
+        P, torch, hv = self._pu_plan(), self.torch, self.hv
+        n, bi = len(self.pus), self.bi_results
+        uni_mv = res["mv"].reshape(n, 2, 2).astype(np.int64)
+        bi_mv = bi["mv"].reshape(n, 2, 2).astype(np.int64)
+        jobs, first = P["jobs"], P["first"]
+        for l in (0, 1):
+            jobs["mvd"][first + l] = 0
+            jobs["mvd"][first + l, l] = res["mvd"][l::2]
+            jobs["mvp_flag"][first + l] = 0
+            jobs["mvp_flag"][first + l, l] = res["mvp_flag"][l::2]
+            jobs["mvd"][first + 2, l] = bi["mvd"][l::2]
+            jobs["mvp_flag"][first + 2, l] = bi["mvp_flag"][l::2]
+        # every block a candidate reads, filter taps included, must lie inside the padded planes
+        for mv in (uni_mv, bi_mv):
+            for c, (size, lim) in enumerate(((self.pus["w"], self.W), (self.pus["h"], self.H))):
+                pos = (self.pus["x0"], self.pus["y0"])[c].astype(np.int64)[:, None] + (mv[:, :, c] >> 2)
+                if (pos - 4 < -self.PAD + 8).any() or (pos + size[:, None] + 4 > lim + self.PAD - 8).any():
+                    raise RuntimeError("pu_modes: a searched vector leaves the padded reference planes")
+        with torch.cuda.stream(hv.tstream):
+            P["d_jobs"].copy_(torch.from_numpy(jobs.view(np.uint8).reshape(-1)))
+            for g in P["groups"]:
+                sel, k = g["sel"], len(g["sel"])
+                for q in g["planes"]:
+                    sh, fr, size = q["shift"], (1 << q["shift"]) - 1, q["size"]
+
+                    def ref(mv, l):
+                        return (q["first_ref"] + l) * q["pe"] + q["here"] + (mv[:, 1] >> sh) * q["stride"] + (mv[:, 0] >> sh)
+
+                    uj = np.zeros((k, 2, 8), np.int32)
+                    bj = np.zeros((k, 12), np.int32)
+                    for l in (0, 1):
+                        mv = uni_mv[sel, l]
+                        uj[:, l, 0], uj[:, l, 1] = (3 * np.arange(k) + l) * size * size, ref(mv, l)
+                        uj[:, l, 2] = uj[:, l, 3] = size
+                        uj[:, l, 4], uj[:, l, 5] = mv[:, 0] & fr, mv[:, 1] & fr
+                        mv = bi_mv[sel, l]
+                        bj[:, 1 + l] = ref(mv, l)
+                        bj[:, 5 + 2 * l], bj[:, 6 + 2 * l] = mv[:, 0] & fr, mv[:, 1] & fr
+                    bj[:, 0] = (3 * np.arange(k) + 2) * size * size
+                    bj[:, 3] = bj[:, 4] = size
+                    q["d_uj"].copy_(torch.from_numpy(uj.reshape(-1)))
+                    q["d_bj"].copy_(torch.from_numpy(bj.reshape(-1)))
+        self._pu_decisions = None
+
+    def pu_mode_launches(self):
+        """measurePuCost and go2's comparison as batches over the tables pu_candidates() uploaded: per unit size and plane HavocPredUni of the L0 and L1 candidates,
+        HavocPredBi of the bi candidate (8-tap luma, 4-tap Cb / Cr) and the Hadamard SATD of all three against the source (as merge_candidates measures it), then the
+        candidates' CABAC bits and the decision.  3 launches per (size, plane) + 2; asynchronous"""
+        hv, bd, P = self.hv, self.bd, self._pu_plan()
+        M = P["M"]
+        for g in P["groups"]:
+            for plane, q in enumerate(g["planes"]):
+                ref = self.d_cpic if plane else self.d_pic
+                hv.pred_uni_d(q["taps"], bd, q["d_dst"], q["size"], ref, q["stride"], q["d_uj"].view(-1, 8), q["size"], q["size"])
+                hv.pred_bi_d(q["taps"], bd, q["d_dst"], q["size"], ref, q["stride"], q["d_bj"].view(-1, 12), q["size"], q["size"])
+                hv.satd_d(ref, q["stride"], q["d_dst"], q["size"], q["d_sj"], P["d_satd"][plane * M + g["at"]:plane * M + g["at"] + g["m"]], q["size"], q["size"])
+        hv.pu_rate_d(self.d_pu_syntax_states, P["d_jobs"], P["slice"], P["d_rate"], P["d_after"])
+        lam_q16 = int(float(self.params.reciprocal_sqrt_lambda) * 65536 + 0.5)      # Lambda::set(double)
+        hv.pu_decide_d(P["d_first"], P["d_count"], len(self.pus), P["d_rate"], P["d_satd"][:M], P["d_satd"][M:2 * M], P["d_satd"][2 * M:], lam_q16, P["d_after"],
+                       P["d_cost"], P["d_best"], P["d_best_cost"], P["d_best_syntax"])
+
+    @property
+    def pu_decisions(self):
+        """what pu_mode_launches() left on the device, as numpy, per unit of self.pus: dict(mode [n] (0 L0, 1 L1, 2 bi), cost [n] (Q16), costs [n, 3], syntax [n, 16]
+        (the winner's snapshot), rates [n, 3] (Q16), satd [n, 3 candidates, 3 planes], jobs [n, 3] (PU_RATE_JOB_DT as uploaded))"""
+        if getattr(self, "_pu_decisions", None) is None:
+            hv, P, K = self.hv, self._pu_plan(), self.PU_CANDIDATES
+            M, at = P["M"], P["first"][:, None] + np.arange(K)[None, :]
+            satd = hv.down(P["d_satd"], np.int32).reshape(3, M)
+            self._pu_decisions = dict(mode=hv.down(P["d_best"], np.int32), cost=hv.down(P["d_best_cost"], np.int64), costs=hv.down(P["d_cost"], np.int64)[at],
+                                      syntax=hv.down(P["d_best_syntax"], np.uint8).reshape(-1, self.hmod.PU_SYNTAX_CTX_BYTES),
+                                      rates=hv.down(P["d_rate"], np.int64)[at], satd=np.stack([satd[c][at] for c in range(3)], 2),
+                                      jobs=hv.down(P["d_jobs"], np.uint8).view(self.hmod.PU_RATE_JOB_DT)[at])
+        return self._pu_decisions
 
     def chroma_chain(self, field):
         """the inter residual of the chroma planes at the decided vectors (turing/Reconstruct.cpp:1274-1286 with cIdx 1, 2): HavocPredUni 4-tap of every unit's
@@ -1180,18 +1329,22 @@ class DecisionPicture:
             # 294 -> 268 / 383 -> 237 pictures/s with 8 / 16 in flight: a second issuing thread per picture costs more than the overlap gives)
             self.intra_decisions()
         self._merge = None
+        if self.pu_modes:
+            self.pu_candidates(res)
         if self.search_on_device:
             # everything after the searches is a FIXED sequence of launches over device-resident tables (the decided field never leaves the device, the decisions
             # between the launches are kernels): recorded once into a HIP graph, one launch per picture, one wait at the end
             self._rqt = self._cells = self._sao_decisions = self._rqt_rates = self._rqt_tree = None
+            pu = (self.pu_mode_launches,) if self.pu_modes else ()      # (the tables its launches read went up before the replay: pu_candidates)
             if self.sao:
                 self._replayed("after the searches", lambda: (self.merge_candidates(field), self.predict(field), self.sao_filter_inputs(field),
-                                                              self.sao_loop_filter()))
+                                                              self.sao_loop_filter(), [f() for f in pu]))
             elif self.tree_rates:      # (the chroma reconstruction is the tree decision's own: chroma_chain, which codes chroma at depth 0 always, does not run)
-                self._replayed("after the searches", lambda: (self.merge_candidates(field), self.predict(field), self.tree_and_filter_on_device()))
+                self._replayed("after the searches", lambda: (self.merge_candidates(field), self.predict(field), self.tree_and_filter_on_device(),
+                                                              [f() for f in pu]))
             else:
                 self._replayed("after the searches", lambda: (self.merge_candidates(field), self.predict(field), self.tree_and_filter_on_device(),
-                                                              self.chroma_chain(field)))
+                                                              self.chroma_chain(field), [f() for f in pu]))
             self.rqt_stats = RqtStats()
             self.rqt_stats.launches, self.rqt_stats.candidates = self.rqt_plan["launches"], 5 * len(self.units)
         else:
@@ -1250,6 +1403,8 @@ class DecisionPicture:
             raise ValueError("step_banded does not price residuals with CABAC rates: use step() with residual_rates=True")
         if self.tree_rates:
             raise ValueError("step_banded does not price transform trees with CABAC rates: use step() with tree_rates=True")
+        if self.pu_modes:
+            raise ValueError("step_banded does not decide the prediction units' modes: use step() with pu_modes=True")
         if self.sao:
             # SAO of band b reads the deblocked rows of band b + 1 (turing/TaskSao.cpp:46-56): not built
             raise ValueError("step_banded does not run SAO: use step() with sao=True")
@@ -1330,8 +1485,11 @@ class DecisionPicture:
             raise RuntimeError("step_banded: a wait on the search's progress gave up; the picture's reconstruction is not to be used")
 
     def results(self):
-        """what the TU chain left on the device, as numpy (per group): coefficients, levels, flags, SSDs; and the reconstruction"""
+        """what the TU chain left on the device, as numpy (per group): coefficients, levels, flags, SSDs; and the reconstruction; with pu_modes=True a third entry,
+        dict(pu_modes=self.pu_decisions)"""
         hv = self.hv
         out = [dict(log2=g["log2"], coef=hv.down(g["coef"], np.int16), level=hv.down(g["level"], np.int16), cbf=hv.down(g["cbf"], np.int32),
                     ssd=hv.down(g["ssd"], np.uint32)) for g in self.groups]
+        if self.pu_modes:
+            return out, hv.down(self.recon, self.dt), dict(pu_modes=self.pu_decisions)
         return out, hv.down(self.recon, self.dt)

@@ -131,6 +131,8 @@ def _load():
         "intra_rate": [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp],
         "intra_rate_jobs": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
         "tree_rate": [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp],
+        "pu_rate": [_vp, _vp, _vp, _i, _vp, _vp, _vp],
+        "pu_decide": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp],
         "intra_decide_rated": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_int32, _vp, _vp],
         "rqt_decide_rated": [_vp, _vp, _i, _vp, _vp, _vp, _vp, C.c_int64, C.c_ssize_t, _i, _i, _vp],
         "rqt_decide_tree": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_ssize_t, _i, C.c_int64, C.c_int64, C.c_ssize_t, _i, _i, _vp, _vp],
@@ -309,6 +311,26 @@ TREE_RATE_JOB_DT = np.dtype([("luma_off", "<i4"), ("cb_off", "<i4"), ("cr_off", 
                              ("pad", "u1", 2), ("reserved", "<i4", 2)])
 assert TREE_RATE_JOB_DT.itemsize == 32
 TREE_RATE_SPLIT_FLAG_CODED = 1
+# one havoc_mi355x_pu_rate_job (include/havoc_mi355x.h), 32 bytes: one candidate of a prediction unit; mvd [list][x, y]; pred: PU_PRED_*; flags: PU_RATE_*
+PU_RATE_JOB_DT = np.dtype([("ctx_index", "<i4"), ("out_index", "<i4"), ("mvd", "<i2", (2, 2)), ("merge_idx", "u1"), ("pred", "u1"), ("mvp_flag", "u1", 2),
+                           ("ref_idx", "u1", 2), ("w", "u1"), ("h", "u1"), ("cqt_depth", "u1"), ("flags", "u1"), ("pad", "u1", 2), ("reserved", "<i4")])
+assert PU_RATE_JOB_DT.itemsize == 32
+PU_RATE_MERGE, PU_RATE_SKIP = 1, 2
+PU_PRED_L0, PU_PRED_L1, PU_PRED_BI = 0, 1, 2
+PU_SYNTAX_CTX_BYTES = 16        # HAVOC_PU_SYNTAX_CTX_*: merge_flag, merge_idx, inter_pred_idc[5], ref_idx_lX[2], abs_mvd_greater0 / 1_flag, mvp_lX_flag, 4 reserved
+
+
+class PuSlice(C.Structure):
+    """havoc_mi355x_pu_slice: the slice-level values Syntax<prediction_unit> reads"""
+    _fields_ = [("slice_b", C.c_int32), ("max_num_merge_cand", C.c_int32), ("mvd_l1_zero_flag", C.c_int32), ("num_ref_idx_active_minus1", C.c_int32 * 2),
+                ("reserved", C.c_int32 * 3)]
+
+    def __init__(self, slice_b=1, max_num_merge_cand=5, mvd_l1_zero_flag=0, num_ref_idx_active_minus1=(0, 0)):
+        super().__init__(int(slice_b), int(max_num_merge_cand), int(mvd_l1_zero_flag), (C.c_int32 * 2)(*[int(v) for v in num_ref_idx_active_minus1]))
+
+
+assert C.sizeof(PuSlice) == 32
+
 # havoc_mi355x_rqt_chroma_at / havoc_mi355x_rqt_tree_choice (include/havoc_mi355x.h), 16 bytes each: where a unit's chroma candidates are / what rqt_decide_tree adds
 RQT_CHROMA_AT_DT = np.dtype([("cb_zero", "<i4"), ("cr_zero", "<i4"), ("cb_one", "<i4"), ("cr_one", "<i4")])
 RQT_TREE_RESULT_DT = np.dtype([("mask_zero", "<u4"), ("mask_one", "<u4"), ("chroma_ssd_zero", "<i4"), ("chroma_ssd_one", "<i4")])
@@ -949,6 +971,47 @@ class Havoc:
                          after, after_sy)
         return (self.down(rates, np.int64)[:nr], self.down(cbf, np.int32)[:nr].view(np.uint32), self.down(after, np.uint8)[:len(jobs) * 128].reshape(-1, 128),
                 self.down(after_sy, np.uint8)[:len(jobs) * INTRA_SYNTAX_CTX_BYTES].reshape(-1, INTRA_SYNTAX_CTX_BYTES))
+
+    def pu_rate_d(self, syntax_states, jobs, slice_params, rates, syntax_out=None):
+        """the CABAC rate of every candidate of prediction units: Syntax<prediction_unit> under Measure<void> (havoc_mi355x_pu_rate); syntax_states: uint8 tensor, 16
+        bytes per snapshot; jobs: uint8 tensor holding PU_RATE_JOB_DT records; slice_params: PuSlice; rates: int64 tensor; syntax_out: None, or 16 bytes per job.  No sync."""
+        self._ck(self.L.havoc_mi355x_pu_rate(self.h, _ptr(syntax_states), _ptr(jobs), jobs.numel() // PU_RATE_JOB_DT.itemsize, C.addressof(slice_params), _ptr(rates),
+                                             _ptr(syntax_out)))
+
+    def pu_rate(self, syntax_states, jobs, slice_params):
+        """numpy level: syntax_states uint8 [k, 16], jobs PU_RATE_JOB_DT array -> (rates int64 [max out_index + 1], the entries no job writes 0; the snapshots after,
+        uint8 [njobs, 16])"""
+        jobs = np.ascontiguousarray(jobs, PU_RATE_JOB_DT)
+        nr = int(jobs["out_index"].max()) + 1 if len(jobs) else 0
+        with self.torch.cuda.stream(self.tstream):
+            sy = self.torch.from_numpy(np.ascontiguousarray(syntax_states, np.uint8).reshape(-1)).to(self.device)
+            j = self.torch.from_numpy(jobs.view(np.uint8).reshape(-1).copy()).to(self.device) if len(jobs) else self.torch.zeros(32, dtype=self.torch.uint8, device=self.device)
+            rates = self.torch.zeros(max(nr, 1), dtype=self.torch.int64, device=self.device)
+            after = self.torch.zeros(max(len(jobs), 1) * PU_SYNTAX_CTX_BYTES, dtype=self.torch.uint8, device=self.device)
+        self._ck(self.L.havoc_mi355x_pu_rate(self.h, _ptr(sy), _ptr(j), len(jobs), C.addressof(slice_params), _ptr(rates), _ptr(after)))
+        return self.down(rates, np.int64)[:nr], self.down(after, np.uint8)[:len(jobs) * PU_SYNTAX_CTX_BYTES].reshape(-1, PU_SYNTAX_CTX_BYTES)
+
+    def pu_decide_d(self, first, count, n, rates, satd_y, satd_cb, satd_cr, lam_q16, syntax_after, cost, best, best_cost, best_syntax=None):
+        """go2's comparison of n prediction units over their contiguous candidates (havoc_mi355x_pu_decide): first / count / best: int32 tensors [n]; rates / cost:
+        int64 tensors per candidate; best_cost: int64 [n]; syntax_after / best_syntax: uint8, 16 bytes per candidate / unit, or None.  No sync."""
+        self._ck(self.L.havoc_mi355x_pu_decide(self.h, _ptr(first), _ptr(count), n, _ptr(rates), _ptr(satd_y), _ptr(satd_cb), _ptr(satd_cr), int(lam_q16),
+                                               _ptr(syntax_after), _ptr(cost), _ptr(best), _ptr(best_cost), _ptr(best_syntax)))
+
+    def pu_decide(self, first, count, rates, satd_y, satd_cb, satd_cr, lam_q16, syntax_after):
+        """numpy level -> (cost int64 per candidate, best int32 [n], best_cost int64 [n], best_syntax uint8 [n, 16])"""
+        n, m = len(first), len(rates)
+        t = self.torch
+        with t.cuda.stream(self.tstream):
+            up = lambda a, dt: t.from_numpy(np.ascontiguousarray(a, dt).reshape(-1)).to(self.device) if np.size(a) else t.zeros(16, dtype=getattr(t, np.dtype(dt).name), device=self.device)
+            f, c, r = up(first, np.int32), up(count, np.int32), up(rates, np.int64)
+            sy, scb, scr, sa = up(satd_y, np.int32), up(satd_cb, np.int32), up(satd_cr, np.int32), up(syntax_after, np.uint8)
+            cost = t.zeros(max(m, 1), dtype=t.int64, device=self.device)
+            best = t.zeros(max(n, 1), dtype=t.int32, device=self.device)
+            best_cost = t.zeros(max(n, 1), dtype=t.int64, device=self.device)
+            best_syntax = t.zeros(max(n, 1) * PU_SYNTAX_CTX_BYTES, dtype=t.uint8, device=self.device)
+        self.pu_decide_d(f, c, n, r, sy, scb, scr, lam_q16, sa, cost, best, best_cost, best_syntax)
+        return (self.down(cost, np.int64)[:m], self.down(best, np.int32)[:n], self.down(best_cost, np.int64)[:n],
+                self.down(best_syntax, np.uint8)[:n * PU_SYNTAX_CTX_BYTES].reshape(-1, PU_SYNTAX_CTX_BYTES))
 
     def intra_rate_jobs_d(self, mpm, order, count, slot, rdoq_jobs, n, flags, jobs):
         """INTRA_RATE_JOB_DT records of the candidates intra_expand laid out (havoc_mi355x_intra_rate_jobs): job c = candidate slot c; jobs: uint8 tensor.  No sync."""

@@ -14,8 +14,9 @@
 // `tuRate` (DecisionPicture(residual_rates=True)).  An INTRA candidate's whole rate can be the reference's too: havoc_mi355x_intra_rate measures what
 // EstimateRateLuma measures for it -- the mode bits in their CABAC state, split_transform_flag, cbf_luma, the residual -- and havoc_mi355x_intra_decide_rated /
 // havoc_search_intra_device_rated decide by it.  The inter tree's WHOLE rate -- split_transform_flag, cbf_cb, cbf_cr, cbf_luma and the Y, Cb, Cr residuals with one
-// CABAC state -- is havoc_mi355x_tree_rate's, and havoc_mi355x_rqt_decide_tree (DecisionPicture(tree_rates=True)) decides by it over three planes.  Still not priced:
-// rqt_root_cbf, the prediction-unit and coding-unit bits, and contexts carried from unit to unit.
+// CABAC state -- is havoc_mi355x_tree_rate's, and havoc_mi355x_rqt_decide_tree (DecisionPicture(tree_rates=True)) decides by it over three planes.  The prediction-unit
+// bits and the mode decision by them are havoc_mi355x_pu_rate / _pu_decide (pu_decision.hpp: decidePu).  Still not priced: rqt_root_cbf, the coding-unit bits, and
+// contexts carried from unit to unit.
 // What is restated here -- and checked against the reference's tables + Rdoq.cpp -- is the
 // order of evaluation, the uncoded short-cut, the cost arithmetic (Q16) and the strict comparison.
 #pragma once
