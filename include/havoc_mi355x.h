@@ -965,6 +965,95 @@ int havoc_mi355x_block_cells(havoc_mi355x_ctx *ctx, int width, int height, int q
 int havoc_mi355x_block_cells_add(havoc_mi355x_ctx *ctx, int width, int height, int qp, int dpb_index0, const int16_t *d_field, const havoc_mi355x_rqt_unit *d_units,
                                  const havoc_mi355x_rqt_choice *d_decisions, int n, havoc_mi355x_cell *d_cells);
 
+/* ---- closing an inter coding unit: the CU's own bits and the residual / no-residual decision (csrc/kernels_cu_rate.hip: k_cu_close, k_unit_pred_ssd) ----
+ * Search<IfCbf<rqt_root_cbf, transform_tree>>::go (turing/Search.hpp:2362-2568): once the transform tree of an inter coding unit is decided, the reference prices the
+ * CU preamble with the values it now knows -- cu_skip_flag, pred_mode_flag, part_mode, rqt_root_cbf (Syntax<coding_unit>, turing/SyntaxCtu.hpp:143-264; writers
+ * turing/Binarization.h:283-375 and the generic flag writer) -- turns a merged 2Nx2N unit without residual into a skipped CU, and compares the coded unit with the same
+ * unit left at its prediction.  One job = one candidate CU, a lane each.  Preconditions: a P or B slice; transquant_bypass_enabled_flag 0 (cu_transquant_bypass_flag is
+ * not coded); no PCM; CuPredMode is MODE_INTER on entry (pred_mode_flag is 0, part_mode takes the inter binarisation).
+ * With haveResidual = (the chosen tree's cbf mask != 0) and merged = HAVOC_CU_CLOSE_MERGE_2Nx2N, in the reference's order (all rates Q16, relative to the CU's start):
+ *   - the coded candidate: rate = the PU rate + cu_skip_flag(0) + pred_mode_flag(0) + part_mode + rqt_root_cbf(1) unless merged (SyntaxCtu.hpp:251-255) + the tree's
+ *     rate; lambdaDistortion = int32(ssdY + ssdCb + ssdCr) * reciprocal_lambda -- the UNWEIGHTED sum reconstructInter returns (turing/Reconstruct.cpp:1427), not the
+ *     ssdY + 4 ssdCb + 4 ssdCr the depth decision inside it compares: the reference's quirk, kept;
+ *   - !haveResidual and merged: a skipped CU (Search.hpp:2421-2441): contexts AND rate go back to those before the CU -- the PU rate is dropped -- then merge_idx when
+ *     MaxNumMergeCand > 1 (priced from the prediction-unit contexts BEFORE the CU), then cu_skip_flag(1); the distortion stays that of the reconstruction;
+ *   - !haveResidual, not merged: PU rate + preamble + rqt_root_cbf(0), no tree;
+ *   - haveResidual: the unit is priced without residual as well (:2462-2531): merged -> cu_skip_flag(1) + merge_idx from the contexts before the CU; not merged -> the
+ *     state after the preamble + rqt_root_cbf(0).  Its lambdaDistortion = lambda * ssdPrediction[0] + lambda * ssdPrediction[1] + lambda * ssdPrediction[2], three
+ *     products.  It replaces the coded candidate on cost < cost (strict: equal costs keep the residual), and the coded residual is then dropped.
+ * part_mode (Binarization.h:311-375): 2Nx2N one bin 1 at ctxInc 0; else 0 at ctxInc 0, bin (~mode >> 1 & 1) at ctxInc 1, then at log2CbSize == MinCbLog2SizeY a third
+ * bin (~mode >> 2 & 1) at ctxInc 2 when log2CbSize > 3 and the mode is not 2NxN -- the reference writes 1 there for NxN as for Nx2N (the standard's NxN has 0): priced
+ * as the reference writes it -- and above MinCbLog2SizeY with amp_enabled_flag the bin (~mode >> 2 & 1) at ctxInc 3 and for an AMP mode one bypass bin.
+ * The context families are pairwise disjoint (turing/Cabac.h:96-136: prediction unit / cu_skip_flag, pred_mode_flag, part_mode, rqt_root_cbf / the tree's), so the sum
+ * of the three rates is the rate of the syntax's interleaved order.
+ * d_cu_syntax holds HAVOC_CU_SYNTAX_CTX_BYTES per snapshot, each byte a ContextModel::state (counts: Cabac.h:96-129): */
+enum {
+    HAVOC_CU_SYNTAX_CTX_SPLIT_CU_FLAG = 0,      /* split_cu_flag [3]: the quadtree step's, passed through */
+    HAVOC_CU_SYNTAX_CTX_CU_SKIP_FLAG = 3,       /* cu_skip_flag [3] */
+    HAVOC_CU_SYNTAX_CTX_PRED_MODE_FLAG = 6,     /* pred_mode_flag [1] */
+    HAVOC_CU_SYNTAX_CTX_PART_MODE = 7,          /* part_mode [4] */
+    HAVOC_CU_SYNTAX_CTX_RQT_ROOT_CBF = 11,      /* rqt_root_cbf [1] */
+    HAVOC_CU_SYNTAX_CTX_BYTES = 16              /* 12..15 reserved: passed through */
+};
+enum {
+    HAVOC_CU_CLOSE_MIN_CB = 1,          /* log2CbSize == MinCbLog2SizeY */
+    HAVOC_CU_CLOSE_AMP = 2,             /* amp_enabled_flag */
+    HAVOC_CU_CLOSE_MERGE_2Nx2N = 4      /* PartMode 2Nx2N with merge_flag: rqt_root_cbf is not coded, the unit may become a skipped CU */
+};
+enum { HAVOC_CU_OUTCOME_REFUSED = -1, HAVOC_CU_OUTCOME_CODED = 0, HAVOC_CU_OUTCOME_NO_RESIDUAL = 1, HAVOC_CU_OUTCOME_SKIPPED = 2 };
+typedef struct {
+    int32_t ctx_index;          /* the snapshot of d_cu_syntax (16 bytes) the CU starts from */
+    int32_t unit_index;         /* i: d_choice[i], d_tree_choice[i], d_tree_rate[2 i + depth], d_pred_ssd[3 i ..] */
+    int32_t pu_rate_index;      /* d_pu_rate[..]: the Q16 rate of the CU's prediction units, summed (havoc_mi355x_pu_rate's of the chosen candidates) */
+    int32_t pu_before_index;    /* the snapshot of d_pu_before (HAVOC_PU_SYNTAX_CTX_*, 16 bytes) before the CU */
+    int32_t pu_after_index;     /* the snapshot of d_pu_after after the CU's prediction units */
+    uint8_t log2_cb_size;       /* 3..6 */
+    uint8_t part_mode;          /* PartMode: 0 2Nx2N, 1 2NxN, 2 Nx2N, 3 NxN, 4 2NxnU, 5 2NxnD, 6 nLx2N, 7 nRx2N */
+    uint8_t skip_ctx_inc;       /* cu_skip_flag's ctxInc, 0..2: the left and upper neighbours' cu_skip_flag summed (Binarization.h:283-295): the caller's */
+    uint8_t merge_idx;          /* read with HAVOC_CU_CLOSE_MERGE_2Nx2N */
+    uint8_t flags;              /* HAVOC_CU_CLOSE_* */
+    uint8_t pad[3];
+    int32_t reserved;
+} havoc_mi355x_cu_close_job;   /* sizeof: 32 */
+typedef struct {
+    int32_t outcome;            /* HAVOC_CU_OUTCOME_* */
+    int32_t have_residual;      /* the chosen tree's cbf mask != 0 (0 for a refused job) */
+    int64_t rate;               /* the winner's: Q16 bits of the whole CU, -1 refused */
+    int64_t lambda_distortion;  /* the winner's Q16 lambdaDistortion */
+    int64_t cost;               /* rate + lambda_distortion (cost2) */
+    int64_t cost_coded;         /* the coded candidate's cost; -1 when the tree has no residual (there is then one candidate only) */
+    int64_t cost_no_residual;   /* the cost of the unit left at its prediction (skipped, or rqt_root_cbf 0) */
+} havoc_mi355x_cu_choice;      /* sizeof: 48; every int64 is -1 for a refused job */
+/* The tree is read where havoc_mi355x_rqt_decide_tree left it: with d = (d_choice[i].depth == 0 && d_choice[i].tried_zero) ? 0 : 1 the chosen tree's mask is
+ * d_tree_choice[i].mask_zero / mask_one, its rate d_tree_rate[2 i + d] (read only with a residual), ssdY = zero.ssd or the sum of one[0..3].ssd, ssdCb + ssdCr =
+ * chroma_ssd_zero / chroma_ssd_one (a unit left without residual at depth 1 has d = 1 and mask_one = 0).  d_pred_ssd[3 i + c]: SSD(source, prediction) of the unit
+ * in plane c (havoc_mi355x_unit_pred_ssd), read only with a residual.
+ * A job the syntax cannot code is refused: outcome and every int64 of its record -1, d_cu_syntax_out its input snapshot, d_pu_syntax_out its pu_after snapshot.  That
+ * is: a `flags` bit other than HAVOC_CU_CLOSE_*; skip_ctx_inc > 2; log2_cb_size outside 3..6, or 3 without HAVOC_CU_CLOSE_MIN_CB (MinCbLog2SizeY >= 3); part_mode > 7;
+ * NxN without HAVOC_CU_CLOSE_MIN_CB or at log2_cb_size 3 (the writer asserts / gives Nx2N's bins); an AMP mode (4..7) with HAVOC_CU_CLOSE_MIN_CB or without
+ * HAVOC_CU_CLOSE_AMP (gives 2NxN's / Nx2N's bins); HAVOC_CU_CLOSE_MERGE_2Nx2N with part_mode != 0 or merge_idx >= max_num_merge_cand; pu_rate_index < 0 or a negative
+ * (refused) d_pu_rate entry; a residual whose tree rate is negative.  The other indices are trusted.
+ * Outputs per job j: d_out[j]; d_cu_syntax_out[16 j ..]: the CU snapshot as the winner left it (the split_cu_flag and reserved bytes as they came); d_pu_syntax_out
+ * [16 j ..]: the prediction-unit snapshot as the winner left it (pu_after; for a skipped CU pu_before with merge_idx moved).  Whether the tree's own contexts (the 128-byte
+ * and 4-byte snapshots of havoc_mi355x_tree_rate) stand is the outcome: they do only for HAVOC_CU_OUTCOME_CODED.
+ * The inputs are never written.  All device pointers 8-byte aligned.  EINVAL: a null pointer; njobs < 0; max_num_merge_cand outside 1..5; a negative lambda; an output
+ * that is one of the inputs.  No allocation, no synchronisation, no workspace: capturable into a HIP graph. */
+int havoc_mi355x_cu_close(havoc_mi355x_ctx *ctx, const uint8_t *d_cu_syntax, const uint8_t *d_pu_before, const uint8_t *d_pu_after, const int64_t *d_pu_rate,
+                          const havoc_mi355x_rqt_choice *d_choice, const havoc_mi355x_rqt_tree_choice *d_tree_choice, const int64_t *d_tree_rate,
+                          const int32_t *d_pred_ssd, const havoc_mi355x_cu_close_job *d_jobs, int njobs, int max_num_merge_cand, int32_t reciprocal_lambda_q16,
+                          havoc_mi355x_cu_choice *d_out, uint8_t *d_cu_syntax_out, uint8_t *d_pu_syntax_out);
+/* ssdPrediction of n units in one launch (turing/Reconstruct.cpp:856 summed over the transform blocks of a unit = SSD(source, prediction) of the unit's block per
+ * plane): d_out[3 i + c] for plane c of unit i, accumulated in int32 as the reference does (wrapping).  Unit i is (1 << log2_size)^2 luma samples at d_src_y +
+ * src_off[0] (rows src_stride apart) against d_pred_y + pred_off[0] (rows pred_stride apart), and half that size in Cb, Cr at d_src_c + src_off[1], [2] (rows
+ * src_stride_c apart) against d_pred_c + pred_off[1], [2] (rows pred_stride_c apart); offsets and strides in samples of 1 (bit_depth 8) or 2 bytes.  log2_size 3..6,
+ * sizes mixed freely.  No alignment is asked of offsets or strides (rows are read in unaligned 8-byte pieces); the records are trusted. */
+typedef struct { int32_t src_off[3], pred_off[3], log2_size, reserved; } havoc_mi355x_pred_ssd_job;     /* sizeof: 32 */
+/* EINVAL: a null pointer, n < 0, a bit depth outside 8..16, a stride that is not positive, d_out one of the inputs.  No allocation, no synchronisation:
+ * capturable into a HIP graph. */
+int havoc_mi355x_unit_pred_ssd(havoc_mi355x_ctx *ctx, int bit_depth, const void *d_src_y, intptr_t src_stride, const void *d_src_c, intptr_t src_stride_c,
+                               const void *d_pred_y, intptr_t pred_stride, const void *d_pred_c, intptr_t pred_stride_c, const havoc_mi355x_pred_ssd_job *d_jobs, int n,
+                               int32_t *d_out);
+
 /* ---- an intra picture's partitions with their real dependencies (round 4; csrc/kernels_decide.hip) ----
  * A partition predicts from the reconstruction of what precedes it (turing/Reconstruct.cpp:609-615) and takes candModeList from its neighbours' decided modes
  * (turing/CandModeList.h:33-95).  A client that runs the batch chain over the partitions level by level (every partition of a level has all its neighbours final)

@@ -5,6 +5,7 @@
 
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 
 using namespace havoc_gpu;
 
@@ -29,6 +30,9 @@ static_assert(sizeof(havoc_mi355x_sao_decision) == 128 && offsetof(havoc_mi355x_
 static_assert(sizeof(havoc_mi355x_residual_rate_job) == 32 && offsetof(havoc_mi355x_residual_rate_job, c_idx) == 12, "job ABI");
 static_assert(sizeof(havoc_mi355x_pu_rate_job) == 32 && offsetof(havoc_mi355x_pu_rate_job, mvd) == 8 && offsetof(havoc_mi355x_pu_rate_job, flags) == 25 &&
               sizeof(havoc_mi355x_pu_slice) == 32, "the prediction-unit rate records are ABI");
+static_assert(sizeof(havoc_mi355x_cu_close_job) == 32 && offsetof(havoc_mi355x_cu_close_job, log2_cb_size) == 20 && offsetof(havoc_mi355x_cu_close_job, flags) == 24 &&
+              sizeof(havoc_mi355x_cu_choice) == 48 && offsetof(havoc_mi355x_cu_choice, rate) == 8 && sizeof(havoc_mi355x_pred_ssd_job) == 32 &&
+              sizeof(havoc_mi355x_rqt_choice) == 104 && sizeof(havoc_mi355x_rqt_tree_choice) == 16, "the coding-unit records are ABI");
 static_assert(sizeof(havoc_mi355x_intra_rate_job) == 32 && offsetof(havoc_mi355x_intra_rate_job, scan_idx) == 12 && offsetof(havoc_mi355x_intra_rate_job, flags) == 15,
               "job ABI");
 static_assert(sizeof(havoc_mi355x_tree_rate_job) == 32 && offsetof(havoc_mi355x_tree_rate_job, out_index) == 16 && offsetof(havoc_mi355x_tree_rate_job, flags) == 21, "job ABI");
@@ -1117,6 +1121,43 @@ int havoc_mi355x_pu_decide(havoc_mi355x_ctx *ctx, const int32_t *d_first, const 
             "pu_decide: d_rate, d_cost, d_best_cost, d_syntax_after and d_best_syntax must be 8-byte aligned");
     return check(launch_pu_decide(LS(ctx), d_first, d_count, n, d_rate, d_satd_y, d_satd_cb, d_satd_cr, reciprocal_sqrt_lambda_q16, d_syntax_after, d_cost, d_best,
                                   d_best_cost, d_best_syntax), "pu_decide");
+}
+
+int havoc_mi355x_cu_close(havoc_mi355x_ctx *ctx, const uint8_t *d_cu_syntax, const uint8_t *d_pu_before, const uint8_t *d_pu_after, const int64_t *d_pu_rate,
+                          const havoc_mi355x_rqt_choice *d_choice, const havoc_mi355x_rqt_tree_choice *d_tree_choice, const int64_t *d_tree_rate,
+                          const int32_t *d_pred_ssd, const havoc_mi355x_cu_close_job *d_jobs, int njobs, int max_num_merge_cand, int32_t reciprocal_lambda_q16,
+                          havoc_mi355x_cu_choice *d_out, uint8_t *d_cu_syntax_out, uint8_t *d_pu_syntax_out)
+{
+    REQUIRE_CTX(); REQUIRE(njobs >= 0, "njobs < 0"); REQUIRE(reciprocal_lambda_q16 >= 0, "reciprocal_lambda_q16 < 0");
+    REQUIRE(d_cu_syntax && d_pu_before && d_pu_after && d_pu_rate && d_choice && d_tree_choice && d_tree_rate && d_pred_ssd && d_jobs && d_out && d_cu_syntax_out &&
+            d_pu_syntax_out, "cu_close: null device pointer");
+    REQUIRE(max_num_merge_cand >= 1 && max_num_merge_cand <= 5, "cu_close: MaxNumMergeCand must be 1..5");
+    const void *ins[] = {d_cu_syntax, d_pu_before, d_pu_after, d_pu_rate, d_choice, d_tree_choice, d_tree_rate, d_pred_ssd, d_jobs};
+    const void *outs[] = {d_out, d_cu_syntax_out, d_pu_syntax_out};
+    uintptr_t bits = 0;
+    for (const void *o : outs)
+    {
+        bits |= reinterpret_cast<uintptr_t>(o);
+        for (const void *i : ins) REQUIRE(o != i, "cu_close: an output must not be one of the inputs (which are never written)");
+    }
+    for (const void *i : ins) bits |= reinterpret_cast<uintptr_t>(i);
+    REQUIRE(d_cu_syntax_out != d_pu_syntax_out && static_cast<void *>(d_out) != d_cu_syntax_out && static_cast<void *>(d_out) != d_pu_syntax_out,
+            "cu_close: the three outputs must be distinct");
+    REQUIRE((bits & 7) == 0, "cu_close: every device pointer must be 8-byte aligned");
+    return check(launch_cu_close(LS(ctx), d_cu_syntax, d_pu_before, d_pu_after, d_pu_rate, d_choice, d_tree_choice, d_tree_rate, d_pred_ssd, d_jobs, njobs,
+                                 max_num_merge_cand, reciprocal_lambda_q16, d_out, d_cu_syntax_out, d_pu_syntax_out), "cu_close");
+}
+
+int havoc_mi355x_unit_pred_ssd(havoc_mi355x_ctx *ctx, int bit_depth, const void *d_src_y, intptr_t src_stride, const void *d_src_c, intptr_t src_stride_c,
+                               const void *d_pred_y, intptr_t pred_stride, const void *d_pred_c, intptr_t pred_stride_c, const havoc_mi355x_pred_ssd_job *d_jobs, int n,
+                               int32_t *d_out)
+{
+    REQUIRE_CTX(); REQUIRE(n >= 0, "n < 0"); REQUIRE(bit_depth >= 8 && bit_depth <= 16, "unit_pred_ssd: bit_depth must be 8..16");
+    REQUIRE(d_src_y && d_src_c && d_pred_y && d_pred_c && d_jobs && d_out, "unit_pred_ssd: null device pointer");
+    for (intptr_t s : {src_stride, src_stride_c, pred_stride, pred_stride_c}) REQUIRE(s > 0, "unit_pred_ssd: a stride must be positive");
+    for (const void *i : {d_src_y, d_src_c, d_pred_y, d_pred_c, static_cast<const void *>(d_jobs)}) REQUIRE(i != d_out, "unit_pred_ssd: d_out must not be one of the inputs");
+    return check(launch_unit_pred_ssd(LS(ctx), bit_depth == 8 ? 1 : 2, d_src_y, src_stride, d_src_c, src_stride_c, d_pred_y, pred_stride, d_pred_c, pred_stride_c, d_jobs, n,
+                                      d_out), "unit_pred_ssd");
 }
 
 } // extern "C"

@@ -351,4 +351,22 @@ template <int S> struct Sample;
 template <> struct Sample<1> { typedef uint8_t T; };
 template <> struct Sample<2> { typedef uint16_t T; };
 
+// sum (a-b)^2 = sum a*a + sum b*b - 2 sum a*b (mod 2^32) over the 8-bit (S == 1) or 16-bit (S == 2) samples of a dword: three unsigned dot instructions
+template <int S>
+__device__ __forceinline__ uint32_t ssd_dword(uint32_t a, uint32_t b, uint32_t acc)
+{
+    if (S == 1)
+    {
+        acc = __builtin_amdgcn_udot4(a, a, acc, false);
+        acc = __builtin_amdgcn_udot4(b, b, acc, false);
+        const uint32_t ab = __builtin_amdgcn_udot4(a, b, 0u, false);
+        return acc - 2u * ab;
+    }
+    const u16x2 va = __builtin_bit_cast(u16x2, a), vb = __builtin_bit_cast(u16x2, b);
+    acc = __builtin_amdgcn_udot2(va, va, acc, false);
+    acc = __builtin_amdgcn_udot2(vb, vb, acc, false);
+    const uint32_t ab = __builtin_amdgcn_udot2(va, vb, 0u, false);
+    return acc - 2u * ab;
+}
+
 } // namespace havoc_gpu

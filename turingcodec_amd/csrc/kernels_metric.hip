@@ -844,23 +844,6 @@ __global__ __launch_bounds__(64 * NW) void k_sad4r(const char *__restrict__ src,
 // sum (a-b)^2 = sum a*a + sum b*b - 2 sum a*b (mod 2^32), three unsigned dot instructions per dword
 // ---------------------------------------------------------------------------------------------------------
 
-template <int S>
-__device__ __forceinline__ uint32_t ssd_dword(uint32_t a, uint32_t b, uint32_t acc)
-{
-    if (S == 1)
-    {
-        acc = __builtin_amdgcn_udot4(a, a, acc, false);
-        acc = __builtin_amdgcn_udot4(b, b, acc, false);
-        const uint32_t ab = __builtin_amdgcn_udot4(a, b, 0u, false);
-        return acc - 2u * ab;
-    }
-    const u16x2 va = __builtin_bit_cast(u16x2, a), vb = __builtin_bit_cast(u16x2, b);
-    acc = __builtin_amdgcn_udot2(va, va, acc, false);
-    acc = __builtin_amdgcn_udot2(vb, vb, acc, false);
-    const uint32_t ab = __builtin_amdgcn_udot2(va, vb, 0u, false);
-    return acc - 2u * ab;
-}
-
 // 16 lanes (one DPP row) per job, four jobs per wavefront, CB-byte chunks per lane -- the SAD kernel's mapping: most
 // SSD calls are 4x4 / 8x8 transform blocks (16 / 64 bytes), far too little for a wavefront each
 template <int S, int CB>

@@ -52,6 +52,10 @@ hipError_t launch_tree_rate(hipStream_t, int log2Cb, int depth, const int16_t *,
 hipError_t launch_pu_rate(hipStream_t, const uint8_t *, const havoc_mi355x_pu_rate_job *, int, const havoc_mi355x_pu_slice *, int64_t *, uint8_t *);
 hipError_t launch_pu_decide(hipStream_t, const int32_t *, const int32_t *, int, const int64_t *, const int32_t *, const int32_t *, const int32_t *, int32_t, const uint8_t *,
                             int64_t *, int32_t *, int64_t *, uint8_t *);
+hipError_t launch_cu_close(hipStream_t, const uint8_t *, const uint8_t *, const uint8_t *, const int64_t *, const havoc_mi355x_rqt_choice *, const havoc_mi355x_rqt_tree_choice *,
+                           const int64_t *, const int32_t *, const havoc_mi355x_cu_close_job *, int, int, int32_t, havoc_mi355x_cu_choice *, uint8_t *, uint8_t *);
+hipError_t launch_unit_pred_ssd(hipStream_t, int S, const void *, long, const void *, long, const void *, long, const void *, long, const havoc_mi355x_pred_ssd_job *, int,
+                                int32_t *);
 hipError_t launch_intra_order(hipStream_t, const int32_t *, const havoc_mi355x_intra_mpm *, int, int32_t, int32_t *, int32_t *, int32_t *, int32_t *);
 hipError_t launch_intra_expand(hipStream_t, const havoc_mi355x_intra_search_job *, const int32_t *, const int32_t *, const int32_t *, const int32_t *, int, int, int, int, int,
                                int, int, int, havoc_mi355x_intra_job *, havoc_mi355x_tu_fused_job *, havoc_mi355x_rdoq_job *, int32_t *, int32_t *);

@@ -462,8 +462,12 @@ class DecisionPicture:
     PAD = 96
 
     def __init__(self, hv, width, height, bit_depth=8, qp=32, seed=11, threads=16, frames=None, density=1.0, intra=True, search_on_device=True, distance=1,
-                 sao=False, residual_rates=False, tree_rates=False, pu_modes=False):
+                 sao=False, residual_rates=False, tree_rates=False, pu_modes=False, cu_close=False):
         import torch
+        if cu_close and not search_on_device:
+            raise ValueError("cu_close=True needs the device route (search_on_device=True)")
+        if cu_close and not (tree_rates and pu_modes):
+            raise ValueError("cu_close=True closes a unit over its tree's and its prediction unit's CABAC bits: it needs tree_rates=True and pu_modes=True")
         if pu_modes and not search_on_device:
             raise ValueError("pu_modes=True needs the device route (search_on_device=True)")
         if sao and not search_on_device:
@@ -483,6 +487,8 @@ class DecisionPicture:
         self.tree_rates = tree_rates
         # every searched prediction unit's inter mode (L0 / L1 / bi) by the reference's CABAC bits and three-plane SATDs (havoc_mi355x_pu_rate / _pu_decide)
         self.pu_modes = pu_modes
+        # every transform-tree unit closed as the reference closes an inter coding unit: the CU's own bits and the residual / no-residual decision (havoc_mi355x_cu_close)
+        self.cu_close = cu_close
         self.sao = sao                                # in-loop SAO between deblocking and padding (sao_filter_inputs / sao_loop_filter)
         from . import havoc as hmod
         from . import workload
@@ -551,6 +557,11 @@ class DecisionPicture:
             self.pu_syntax_states = np.clip(prng.integers(4, 100, hmod.PU_SYNTAX_CTX_BYTES)[None, :] +
                                             prng.integers(-6, 7, (self.cx * self.cy, hmod.PU_SYNTAX_CTX_BYTES)), 0, 125).astype(np.uint8)
             self.d_pu_syntax_states = hv.up(self.pu_syntax_states.reshape(-1))
+        if cu_close:        # coding_unit()'s contexts (HAVOC_CU_SYNTAX_CTX_*), per CTU, seeded the same way
+            crng = np.random.default_rng(seed + 7937)
+            self.cu_syntax_states = np.clip(crng.integers(4, 100, hmod.CU_SYNTAX_CTX_BYTES)[None, :] +
+                                            crng.integers(-6, 7, (self.cx * self.cy, hmod.CU_SYNTAX_CTX_BYTES)), 0, 125).astype(np.uint8)
+            self.d_cu_syntax_states = hv.up(self.cu_syntax_states.reshape(-1))
         self.pred = hv.zeros(width * height, self.dt)
         self.recon = hv.zeros(self.pe, self.dt)
         # chroma (round 4): Cb / Cr of source, list 0, list 1 in ONE allocation (plane k at k * cpe: 0-2 Cb, 3-5 Cr), their prediction and reconstruction planes
@@ -830,6 +841,61 @@ class DecisionPicture:
                                       rates=hv.down(P["d_rate"], np.int64)[at], satd=np.stack([satd[c][at] for c in range(3)], 2),
                                       jobs=hv.down(P["d_jobs"], np.uint8).view(self.hmod.PU_RATE_JOB_DT)[at])
         return self._pu_decisions
+
+    # ---- closing every transform-tree unit as an inter coding unit (Search<IfCbf<rqt_root_cbf, transform_tree>>::go, turing/Search.hpp:2362-2568) -------------
+    def _cu_plan(self):
+        """cu_close's job tables and buffers, built once: one job per unit of self.units (the units that have a transform tree), 2Nx2N, not merged, cu_skip_flag's
+        context increment 0, from the CTU's snapshots.  The PU rate charged is that of the L0 candidate of the SEARCHED unit of the same place and size (predict() keeps
+        the list-0 vector: that is the prediction the tree's residual was made from); a tree unit the search did not visit at that size has no prediction-unit rate
+        (pu_rate_index -1) and its record comes back refused."""
+        if hasattr(self, "cu_plan"):
+            return self.cu_plan
+        hv, torch, hmod = self.hv, self.torch, self.hmod
+        u, pus, P = self.units, self.pus, self._pu_plan()
+        n = len(u)
+        at = {(int(p["x0"]), int(p["y0"]), int(p["w"])): i for i, p in enumerate(pus) if p["part_2Nx2N"] == 1 and p["w"] == p["h"]}
+        match = np.array([at.get((int(x), int(y), 1 << int(l)), -1) for x, y, l in zip(u["x0"], u["y0"], u["log2_size"])], np.int64)
+        cand = np.where(match >= 0, P["first"][np.maximum(match, 0)], 0)          # the unit's L0 candidate
+        jobs = np.zeros(n, hmod.CU_CLOSE_JOB_DT)
+        jobs["ctx_index"] = jobs["pu_before_index"] = u["ctx_index"]
+        jobs["unit_index"], jobs["pu_rate_index"], jobs["pu_after_index"] = np.arange(n), np.where(match >= 0, cand, -1), cand
+        jobs["log2_cb_size"], jobs["flags"] = u["log2_size"], np.where(u["log2_size"] == 3, hmod.CU_CLOSE_MIN_CB, 0)
+        x, y = u["x0"].astype(np.int64), u["y0"].astype(np.int64)
+        hw, hh, c2 = self.W // 2, self.H // 2, self.PAD // 2
+        sj = np.zeros(n, hmod.PRED_SSD_JOB_DT)
+        here_c = (y // 2 + c2) * self.cstride + x // 2 + c2
+        sj["src_off"] = np.stack([(y + self.PAD) * self.stride + x + self.PAD, here_c, 3 * self.cpe + here_c], 1)
+        sj["pred_off"] = np.stack([y * self.W + x, (y // 2) * hw + x // 2, hw * hh + (y // 2) * hw + x // 2], 1)
+        sj["log2_size"] = u["log2_size"]
+        with torch.cuda.stream(hv.tstream):
+            up = lambda a: torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).to(hv.device)
+            self.cu_plan = dict(jobs=jobs, ssd_jobs=sj, match=match, d_jobs=up(jobs), d_ssd_jobs=up(sj), d_pred_ssd=hv.zeros(3 * n, np.int32),
+                                d_out=hv.zeros(n * hmod.CU_CHOICE_DT.itemsize, np.uint8), d_cu_after=hv.zeros(n * hmod.CU_SYNTAX_CTX_BYTES, np.uint8),
+                                d_pu_after=hv.zeros(n * hmod.PU_SYNTAX_CTX_BYTES, np.uint8))
+        return self.cu_plan
+
+    def cu_close_launches(self):
+        """ssdPrediction of every unit in three planes (source against pred / cpred), then the close over what rqt_decide_tree, pu_rate and that launch left on the
+        device.  2 launches; asynchronous"""
+        hv, Q, P, R = self.hv, self._cu_plan(), self._pu_plan(), self.rqt_plan
+        hv.unit_pred_ssd_d(self.bd, self.d_pic, self.stride, self.d_cpic, self.cstride, self.pred, self.W, self.cpred, self.W // 2, Q["d_ssd_jobs"], Q["d_pred_ssd"])
+        hv.cu_close_d(self.d_cu_syntax_states, self.d_pu_syntax_states, P["d_after"], P["d_rate"], R["d_out"], R["d_tree_out"], R["tree_rate"], Q["d_pred_ssd"],
+                      Q["d_jobs"], P["slice"].max_num_merge_cand, R["rl_q16"], Q["d_out"], Q["d_cu_after"], Q["d_pu_after"])
+
+    @property
+    def cu_decisions(self):
+        """what cu_close_launches() left on the device, as numpy, per unit of self.units: dict(records (havoc.CU_CHOICE_DT [n]), cu_syntax [n, 16], pu_syntax [n, 16]
+        (the snapshots as the winner left them), pred_ssd int32 [n, 3], jobs (CU_CLOSE_JOB_DT as uploaded), searched [n] (the index in self.pus of the searched unit
+        whose L0 rate was charged, -1: none, the record is refused))"""
+        if not self.cu_close:
+            raise ValueError("cu_decisions: the picture was made without cu_close=True")
+        if getattr(self, "_cu_decisions", None) is None:
+            hv, Q, hmod = self.hv, self._cu_plan(), self.hmod
+            self._cu_decisions = dict(records=hv.down(Q["d_out"], np.uint8).view(hmod.CU_CHOICE_DT).copy(),
+                                      cu_syntax=hv.down(Q["d_cu_after"], np.uint8).reshape(-1, hmod.CU_SYNTAX_CTX_BYTES),
+                                      pu_syntax=hv.down(Q["d_pu_after"], np.uint8).reshape(-1, hmod.PU_SYNTAX_CTX_BYTES),
+                                      pred_ssd=hv.down(Q["d_pred_ssd"], np.int32).reshape(-1, 3), jobs=Q["jobs"], searched=Q["match"])
+        return self._cu_decisions
 
     def chroma_chain(self, field):
         """the inter residual of the chroma planes at the decided vectors (turing/Reconstruct.cpp:1274-1286 with cIdx 1, 2): HavocPredUni 4-tap of every unit's
@@ -1334,8 +1400,9 @@ class DecisionPicture:
         if self.search_on_device:
             # everything after the searches is a FIXED sequence of launches over device-resident tables (the decided field never leaves the device, the decisions
             # between the launches are kernels): recorded once into a HIP graph, one launch per picture, one wait at the end
-            self._rqt = self._cells = self._sao_decisions = self._rqt_rates = self._rqt_tree = None
+            self._rqt = self._cells = self._sao_decisions = self._rqt_rates = self._rqt_tree = self._cu_decisions = None
             pu = (self.pu_mode_launches,) if self.pu_modes else ()      # (the tables its launches read went up before the replay: pu_candidates)
+            pu += (self.cu_close_launches,) if self.cu_close else ()     # (after the tree decisions AND the prediction units' rates: it reads both in place)
             if self.sao:
                 self._replayed("after the searches", lambda: (self.merge_candidates(field), self.predict(field), self.sao_filter_inputs(field),
                                                               self.sao_loop_filter(), [f() for f in pu]))
@@ -1405,6 +1472,8 @@ class DecisionPicture:
             raise ValueError("step_banded does not price transform trees with CABAC rates: use step() with tree_rates=True")
         if self.pu_modes:
             raise ValueError("step_banded does not decide the prediction units' modes: use step() with pu_modes=True")
+        if self.cu_close:
+            raise ValueError("step_banded does not close coding units: use step() with cu_close=True")
         if self.sao:
             # SAO of band b reads the deblocked rows of band b + 1 (turing/TaskSao.cpp:46-56): not built
             raise ValueError("step_banded does not run SAO: use step() with sao=True")
@@ -1486,10 +1555,13 @@ class DecisionPicture:
 
     def results(self):
         """what the TU chain left on the device, as numpy (per group): coefficients, levels, flags, SSDs; and the reconstruction; with pu_modes=True a third entry,
-        dict(pu_modes=self.pu_decisions)"""
+        dict(pu_modes=self.pu_decisions), with cu_close=True also cu_close=self.cu_decisions"""
         hv = self.hv
         out = [dict(log2=g["log2"], coef=hv.down(g["coef"], np.int16), level=hv.down(g["level"], np.int16), cbf=hv.down(g["cbf"], np.int32),
                     ssd=hv.down(g["ssd"], np.uint32)) for g in self.groups]
         if self.pu_modes:
-            return out, hv.down(self.recon, self.dt), dict(pu_modes=self.pu_decisions)
+            extra = dict(pu_modes=self.pu_decisions)
+            if self.cu_close:
+                extra["cu_close"] = self.cu_decisions
+            return out, hv.down(self.recon, self.dt), extra
         return out, hv.down(self.recon, self.dt)

@@ -133,6 +133,8 @@ def _load():
         "tree_rate": [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp],
         "pu_rate": [_vp, _vp, _vp, _i, _vp, _vp, _vp],
         "pu_decide": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp],
+        "cu_close": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_int32, _vp, _vp, _vp],
+        "unit_pred_ssd": [_vp, _i, _vp, C.c_ssize_t, _vp, C.c_ssize_t, _vp, C.c_ssize_t, _vp, C.c_ssize_t, _vp, _i, _vp],
         "intra_decide_rated": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_int32, _vp, _vp],
         "rqt_decide_rated": [_vp, _vp, _i, _vp, _vp, _vp, _vp, C.c_int64, C.c_ssize_t, _i, _i, _vp],
         "rqt_decide_tree": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_ssize_t, _i, C.c_int64, C.c_int64, C.c_ssize_t, _i, _i, _vp, _vp],
@@ -331,6 +333,17 @@ class PuSlice(C.Structure):
 
 assert C.sizeof(PuSlice) == 32
 
+# one havoc_mi355x_cu_close_job / havoc_mi355x_cu_choice / havoc_mi355x_pred_ssd_job (include/havoc_mi355x.h): a candidate coding unit, what closing it gave, a unit's
+# three blocks of source and prediction
+CU_CLOSE_JOB_DT = np.dtype([("ctx_index", "<i4"), ("unit_index", "<i4"), ("pu_rate_index", "<i4"), ("pu_before_index", "<i4"), ("pu_after_index", "<i4"),
+                            ("log2_cb_size", "u1"), ("part_mode", "u1"), ("skip_ctx_inc", "u1"), ("merge_idx", "u1"), ("flags", "u1"), ("pad", "u1", 3), ("reserved", "<i4")])
+CU_CHOICE_DT = np.dtype([("outcome", "<i4"), ("have_residual", "<i4"), ("rate", "<i8"), ("lambda_distortion", "<i8"), ("cost", "<i8"), ("cost_coded", "<i8"),
+                         ("cost_no_residual", "<i8")])
+PRED_SSD_JOB_DT = np.dtype([("src_off", "<i4", 3), ("pred_off", "<i4", 3), ("log2_size", "<i4"), ("reserved", "<i4")])
+assert CU_CLOSE_JOB_DT.itemsize == 32 and CU_CHOICE_DT.itemsize == 48 and PRED_SSD_JOB_DT.itemsize == 32
+CU_CLOSE_MIN_CB, CU_CLOSE_AMP, CU_CLOSE_MERGE_2Nx2N = 1, 2, 4
+CU_OUTCOME_REFUSED, CU_OUTCOME_CODED, CU_OUTCOME_NO_RESIDUAL, CU_OUTCOME_SKIPPED = -1, 0, 1, 2
+CU_SYNTAX_CTX_BYTES = 16        # HAVOC_CU_SYNTAX_CTX_*: split_cu_flag[3], cu_skip_flag[3], pred_mode_flag, part_mode[4], rqt_root_cbf, 4 reserved
 # havoc_mi355x_rqt_chroma_at / havoc_mi355x_rqt_tree_choice (include/havoc_mi355x.h), 16 bytes each: where a unit's chroma candidates are / what rqt_decide_tree adds
 RQT_CHROMA_AT_DT = np.dtype([("cb_zero", "<i4"), ("cr_zero", "<i4"), ("cb_one", "<i4"), ("cr_one", "<i4")])
 RQT_TREE_RESULT_DT = np.dtype([("mask_zero", "<u4"), ("mask_one", "<u4"), ("chroma_ssd_zero", "<i4"), ("chroma_ssd_one", "<i4")])
@@ -1012,6 +1025,51 @@ class Havoc:
         self.pu_decide_d(f, c, n, r, sy, scb, scr, lam_q16, sa, cost, best, best_cost, best_syntax)
         return (self.down(cost, np.int64)[:m], self.down(best, np.int32)[:n], self.down(best_cost, np.int64)[:n],
                 self.down(best_syntax, np.uint8)[:n * PU_SYNTAX_CTX_BYTES].reshape(-1, PU_SYNTAX_CTX_BYTES))
+
+    def cu_close_d(self, cu_syntax, pu_before, pu_after, pu_rate, choice, tree_choice, tree_rate, pred_ssd, jobs, max_num_merge_cand, lam_q16, out, cu_syntax_out,
+                   pu_syntax_out):
+        """closes candidate inter coding units (havoc_mi355x_cu_close): the CU's own CABAC bits and the reference's residual / no-residual / skip decision over what
+        rqt_decide_tree (choice: RQT_RESULT records, tree_choice: RQT_TREE_RESULT_DT, tree_rate int64 [2 units]), pu_rate (pu_rate int64, pu_after) and unit_pred_ssd
+        (pred_ssd int32 [3 units]) left on the device; jobs: uint8 tensor of CU_CLOSE_JOB_DT; out: uint8 tensor of CU_CHOICE_DT; the snapshots uint8, 16 bytes each.  No sync."""
+        self._ck(self.L.havoc_mi355x_cu_close(self.h, _ptr(cu_syntax), _ptr(pu_before), _ptr(pu_after), _ptr(pu_rate), _ptr(choice), _ptr(tree_choice), _ptr(tree_rate),
+                                              _ptr(pred_ssd), _ptr(jobs), jobs.numel() // CU_CLOSE_JOB_DT.itemsize, int(max_num_merge_cand), int(lam_q16), _ptr(out),
+                                              _ptr(cu_syntax_out), _ptr(pu_syntax_out)))
+
+    def cu_close(self, cu_syntax, pu_before, pu_after, pu_rate, choice, tree_choice, tree_rate, pred_ssd, jobs, max_num_merge_cand, lam_q16):
+        """numpy level: the inputs as arrays (choice: 104-byte records as uint8 [n, 104] or a structured array) -> (CU_CHOICE_DT [njobs], cu snapshots uint8 [njobs, 16],
+        pu snapshots uint8 [njobs, 16])"""
+        t = self.torch
+        jobs = np.ascontiguousarray(jobs, CU_CLOSE_JOB_DT)
+        n = len(jobs)
+        with t.cuda.stream(self.tstream):
+            up = lambda a: t.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(self.device) if np.size(a) else t.zeros(128, dtype=t.uint8, device=self.device)
+            ins = [up(a) for a in (cu_syntax, pu_before, pu_after, pu_rate, choice, tree_choice, tree_rate, pred_ssd)]
+            j = up(jobs)
+            out = t.zeros(max(n, 1) * CU_CHOICE_DT.itemsize, dtype=t.uint8, device=self.device)
+            cu_out = t.zeros(max(n, 1) * 16, dtype=t.uint8, device=self.device)
+            pu_out = t.zeros(max(n, 1) * 16, dtype=t.uint8, device=self.device)
+        self._ck(self.L.havoc_mi355x_cu_close(self.h, *[_ptr(a) for a in ins], _ptr(j), n, int(max_num_merge_cand), int(lam_q16), _ptr(out), _ptr(cu_out), _ptr(pu_out)))
+        return (self.down(out, np.uint8)[:n * 48].view(CU_CHOICE_DT).copy(), self.down(cu_out, np.uint8)[:n * 16].reshape(-1, 16), self.down(pu_out, np.uint8)[:n * 16].reshape(-1, 16))
+
+    def unit_pred_ssd_d(self, bit_depth, src_y, src_stride, src_c, src_stride_c, pred_y, pred_stride, pred_c, pred_stride_c, jobs, out):
+        """SSD(source, prediction) of units' luma, Cb and Cr blocks in one launch (havoc_mi355x_unit_pred_ssd); jobs: uint8 tensor of PRED_SSD_JOB_DT; out: int32 [3 n].
+        No sync."""
+        self._ck(self.L.havoc_mi355x_unit_pred_ssd(self.h, bit_depth, _ptr(src_y), src_stride, _ptr(src_c), src_stride_c, _ptr(pred_y), pred_stride, _ptr(pred_c),
+                                                   pred_stride_c, _ptr(jobs), jobs.numel() // PRED_SSD_JOB_DT.itemsize, _ptr(out)))
+
+    def unit_pred_ssd(self, bit_depth, src_y, src_stride, src_c, src_stride_c, pred_y, pred_stride, pred_c, pred_stride_c, jobs):
+        """numpy level: the four sample arrays (uint8, or uint16 above 8 bits) and PRED_SSD_JOB_DT jobs -> int32 [n, 3]"""
+        t, dt = self.torch, np.uint8 if bit_depth == 8 else np.uint16
+        jobs = np.ascontiguousarray(jobs, PRED_SSD_JOB_DT)
+        n = len(jobs)
+        with t.cuda.stream(self.tstream):
+            up = lambda a: t.from_numpy(np.ascontiguousarray(a, dt).reshape(-1).view(np.uint8).copy()).to(self.device)
+            planes = [up(a) for a in (src_y, src_c, pred_y, pred_c)]
+            j = t.from_numpy(jobs.view(np.uint8).reshape(-1).copy()).to(self.device) if n else t.zeros(32, dtype=t.uint8, device=self.device)
+            out = t.zeros(3 * max(n, 1), dtype=t.int32, device=self.device)
+        self._ck(self.L.havoc_mi355x_unit_pred_ssd(self.h, bit_depth, _ptr(planes[0]), src_stride, _ptr(planes[1]), src_stride_c, _ptr(planes[2]), pred_stride,
+                                                   _ptr(planes[3]), pred_stride_c, _ptr(j), n, _ptr(out)))
+        return self.down(out, np.int32)[:3 * n].reshape(-1, 3)
 
     def intra_rate_jobs_d(self, mpm, order, count, slot, rdoq_jobs, n, flags, jobs):
         """INTRA_RATE_JOB_DT records of the candidates intra_expand laid out (havoc_mi355x_intra_rate_jobs): job c = candidate slot c; jobs: uint8 tensor.  No sync."""
