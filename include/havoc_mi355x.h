@@ -1054,6 +1054,77 @@ int havoc_mi355x_unit_pred_ssd(havoc_mi355x_ctx *ctx, int bit_depth, const void 
                                const void *d_pred_y, intptr_t pred_stride, const void *d_pred_c, intptr_t pred_stride_c, const havoc_mi355x_pred_ssd_job *d_jobs, int n,
                                int32_t *d_out);
 
+/* ---- the coding quadtree of every CTU: split_cu_flag's bits and the full / split decision (csrc/kernels_cqt.hip: k_cqt_decide) ----
+ * Search<coding_quadtree>::go (turing/Search.hpp:709-887, the decision :808-886) over Syntax<coding_quadtree>::go (turing/SyntaxCtu.hpp:95-139) and the writer of
+ * split_cu_flag (turing/Binarization.h:102-122), for a whole picture in one call.  The candidate coding units are the caller's: closed units as
+ * havoc_mi355x_cu_close left them, read in place (outcome, rate, lambda_distortion), and a table that says which record, if any, is the candidate of each node.
+ * Geometry: a CTU is a quadtree of L = ctb_log2 - min_cb_log2 + 1 levels and N = 1 + 4 + ... + 4^(L - 1) nodes (1, 5, 21 or 85); node (d, z) -- depth d, z its z-order
+ * index among the 4^d nodes of that depth -- has index (4^d - 1) / 3 + z; its children are (d + 1, 4 z + 0..3) in the order upper left, upper right, lower left,
+ * lower right.  d_node_cu[c * N + k] is the index in d_choice of node k of CTU c (raster order), or -1: no candidate; an index >= n_choice and a record whose
+ * outcome is HAVOC_CU_OUTCOME_REFUSED count as no candidate too.
+ * A node at depth d, in the reference's order:
+ *   - split_cu_flag is coded only when the node lies wholly inside the picture and is larger than MinCb (SyntaxCtu.hpp:97-102); else it is inferred: 1 for a node
+ *     that crosses the picture edge (mustSplit, Search.hpp:810-823: the children are walked, nothing is compared), 0 at MinCb.  One context-coded bin, priced as
+ *     measureEncodeDecision, ctxInc = (CtDepth left of (x0, y0) > d) + (CtDepth above (x0, y0) > d), three contexts (turing/Cabac.h:96) nothing else uses.
+ *   - else the full candidate from the state before the node: split_cu_flag(0) where coded, then the coding unit (its rate and lambdaDistortion; CtDepth of its cells
+ *     becomes d).  It is skipped when the node has no candidate: the reference's testFull == false (:794-806, reached there through rcudepth only), generalised.
+ *   - the split is tried when there is no full candidate, or when the node is larger than MinCb and not (HAVOC_CQT_ECU and the full candidate is a skipped CU,
+ *     :852-855; Speed::trySplit is always true) and some node below it has a candidate.  That last condition is the reference's testSplit == false (:795-801,
+ *     reached there through rcudepth only), generalised like testFull: a caller that has no candidate anywhere below a node has nothing to compare the node's
+ *     unit with, and the unit stands (HAVOC_CQT_NODE_NO_SPLIT_CANDIDATE).  It starts again from the state before the node: split_cu_flag(1) where coded, then the four children in z-order,
+ *     each from the contexts and CtDepth its predecessor left.  A child whose origin lies outside the picture is a Deleted<coding_quadtree> (SyntaxCtu.hpp:119-135):
+ *     no bits, no context, no CtDepth.
+ *   - the split replaces the full candidate on cost2() < cost2() (:875; strict: equal costs keep the single CU); the winner's contexts, rate, lambdaDistortion and
+ *     CtDepth stand.  The reference compares the costs of the whole CTU so far; both candidates carry the same prefix, so comparing the node's own
+ *     rate + lambdaDistortion -- cost_full, cost_split below -- is the same comparison.
+ * CtDepth as the snake answers it (Neighbourhood::snake, turing/StateSpatial.h:49-54, read at MinCb / 2 resolution; pinned by tests/cqt_shim.cpp): preCtu resets every
+ * entry of the picture's upper row and left column to CtDepth -1 at the slice's first CTU (turing/StatePictures.h:1086-1101), so a neighbour outside the picture --
+ * left of column 0, above row 0: no other is ever read -- answers -1 and adds nothing to ctxInc, and so does every neighbour at the picture's first row and column; a
+ * neighbour inside the picture answers the depth of the coding unit that covers it, across CTU borders (the upper CTU's lowest cells, the left CTU's rightmost).
+ * Between CTUs (StatePictures.h:1042-1075, 1108-1115): with HAVOC_CQT_WPP row r starts from the three contexts after CTU (1, r - 1), or from the slice's
+ * (d_cu_syntax) when the picture is one CTU wide; without it row r starts where row r - 1 ended.  One slice, one tile.
+ * A CTU is refused when a node at MinCb that the walk reaches has no candidate (an ecu stop always has its candidate, the skipped CU: it cannot lack one): decided = 0,
+ * every other field of its record and all its node records 0, its CtDepth cells 0, the contexts leave it as they came.
+ * Outputs: d_ctu[c]; d_node[c * N + k]; d_depth: one int8 per MinCb cell, (ctus_y << (L - 1)) rows of (ctus_x << (L - 1)) cells -- whole CTUs; a cell outside the
+ * picture is 0; d_cu_syntax_out[16 c ..]: the snapshot after CTU c, bytes HAVOC_CU_SYNTAX_CTX_SPLIT_CU_FLAG .. + 2 moved, the other thirteen d_cu_syntax's. */
+enum { HAVOC_CQT_WPP = 1, HAVOC_CQT_ECU = 2 };
+enum { HAVOC_CQT_NOT_VISITED = 0, HAVOC_CQT_CU = 1, HAVOC_CQT_SPLIT = 2, HAVOC_CQT_DELETED = 3 };
+enum {
+    HAVOC_CQT_NODE_FINAL = 1,           /* the node belongs to the decided tree (every ancestor's choice is HAVOC_CQT_SPLIT) */
+    HAVOC_CQT_NODE_FLAG_CODED = 2,      /* split_cu_flag was coded (priced), at ctx_inc */
+    HAVOC_CQT_NODE_MUST_SPLIT = 4,      /* the node crosses the picture edge */
+    HAVOC_CQT_NODE_ECU_STOP = 8,        /* HAVOC_CQT_ECU and a skipped CU: the split was not tried */
+    HAVOC_CQT_NODE_NO_CANDIDATE = 16,   /* no full candidate: the split was taken without a comparison */
+    HAVOC_CQT_NODE_NO_SPLIT_CANDIDATE = 32  /* a full candidate and no candidate at any node below: the split was not tried */
+};
+typedef struct {
+    int32_t decided;            /* 1; 0: the CTU is refused, or a wait of the call gave up (then EVERY record of the call has 0) */
+    int32_t n_cus;              /* coding units of the decided tree */
+    int64_t rate;               /* Q16 bits of the CTU's coding quadtree: the units' rates and the coded flags */
+    int64_t flag_rate;          /* the coded split_cu_flags of the decided tree alone */
+    int64_t lambda_distortion;
+    int64_t cost;               /* rate + lambda_distortion */
+} havoc_mi355x_cqt_ctu;         /* sizeof: 40 */
+typedef struct {
+    uint8_t choice;             /* HAVOC_CQT_*: the winner at this node */
+    uint8_t flags;              /* HAVOC_CQT_NODE_* */
+    uint8_t ctx_inc;            /* read with HAVOC_CQT_NODE_FLAG_CODED */
+    uint8_t pad[5];
+    int64_t cost_full;          /* the node as one coding unit: split_cu_flag(0) where coded + the unit's rate + lambdaDistortion; -1: not tried */
+    int64_t cost_split;         /* split_cu_flag(1) where coded + the four children's winners; -1: not tried */
+} havoc_mi355x_cqt_node;        /* sizeof: 24 */
+/* d_work: havoc_mi355x_cqt_decide_workspace(n_ctus) bytes, 8-byte aligned: one 64-bit word per CTU -- bit 63 done, bits 0..23 the three context states after it,
+ * published with an agent-scope release store once the CTU's CtDepth cells are written -- then the row ticket and the give-up word (int32 each).  The call resets it
+ * itself.  Rows are taken by ticket in the order workgroups start; every wait on the row above is bounded, and one that gives up raises the give-up word: every
+ * d_ctu record then comes back with decided = 0 and nothing else of the call is to be used.
+ * The inputs are never written.  EINVAL: a null pointer; width or height that is not a positive multiple of 1 << min_cb_log2; ctb_log2 outside 4..6; min_cb_log2
+ * outside 3..ctb_log2; a flags bit other than HAVOC_CQT_*; n_choice < 0; a workspace that is misaligned or too small; an output that is one of the inputs or another
+ * output.  No allocation, no synchronisation: capturable into a HIP graph. */
+size_t havoc_mi355x_cqt_decide_workspace(int n_ctus);
+int havoc_mi355x_cqt_decide(havoc_mi355x_ctx *ctx, int width, int height, int ctb_log2, int min_cb_log2, int flags, const uint8_t *d_cu_syntax,
+                            const int32_t *d_node_cu, const havoc_mi355x_cu_choice *d_choice, int n_choice, void *d_work, size_t work_bytes,
+                            havoc_mi355x_cqt_ctu *d_ctu, havoc_mi355x_cqt_node *d_node, int8_t *d_depth, uint8_t *d_cu_syntax_out);
+
 /* ---- an intra picture's partitions with their real dependencies (round 4; csrc/kernels_decide.hip) ----
  * A partition predicts from the reconstruction of what precedes it (turing/Reconstruct.cpp:609-615) and takes candModeList from its neighbours' decided modes
  * (turing/CandModeList.h:33-95).  A client that runs the batch chain over the partitions level by level (every partition of a level has all its neighbours final)

@@ -33,6 +33,8 @@ static_assert(sizeof(havoc_mi355x_pu_rate_job) == 32 && offsetof(havoc_mi355x_pu
 static_assert(sizeof(havoc_mi355x_cu_close_job) == 32 && offsetof(havoc_mi355x_cu_close_job, log2_cb_size) == 20 && offsetof(havoc_mi355x_cu_close_job, flags) == 24 &&
               sizeof(havoc_mi355x_cu_choice) == 48 && offsetof(havoc_mi355x_cu_choice, rate) == 8 && sizeof(havoc_mi355x_pred_ssd_job) == 32 &&
               sizeof(havoc_mi355x_rqt_choice) == 104 && sizeof(havoc_mi355x_rqt_tree_choice) == 16, "the coding-unit records are ABI");
+static_assert(sizeof(havoc_mi355x_cqt_ctu) == 40 && offsetof(havoc_mi355x_cqt_ctu, rate) == 8 && sizeof(havoc_mi355x_cqt_node) == 24 &&
+              offsetof(havoc_mi355x_cqt_node, cost_full) == 8 && offsetof(havoc_mi355x_cu_choice, lambda_distortion) == 16, "the coding-quadtree records are ABI");
 static_assert(sizeof(havoc_mi355x_intra_rate_job) == 32 && offsetof(havoc_mi355x_intra_rate_job, scan_idx) == 12 && offsetof(havoc_mi355x_intra_rate_job, flags) == 15,
               "job ABI");
 static_assert(sizeof(havoc_mi355x_tree_rate_job) == 32 && offsetof(havoc_mi355x_tree_rate_job, out_index) == 16 && offsetof(havoc_mi355x_tree_rate_job, flags) == 21, "job ABI");
@@ -1158,6 +1160,39 @@ int havoc_mi355x_unit_pred_ssd(havoc_mi355x_ctx *ctx, int bit_depth, const void 
     for (const void *i : {d_src_y, d_src_c, d_pred_y, d_pred_c, static_cast<const void *>(d_jobs)}) REQUIRE(i != d_out, "unit_pred_ssd: d_out must not be one of the inputs");
     return check(launch_unit_pred_ssd(LS(ctx), bit_depth == 8 ? 1 : 2, d_src_y, src_stride, d_src_c, src_stride_c, d_pred_y, pred_stride, d_pred_c, pred_stride_c, d_jobs, n,
                                       d_out), "unit_pred_ssd");
+}
+
+size_t havoc_mi355x_cqt_decide_workspace(int n_ctus) { return cqt_decide_workspace_bytes(n_ctus); }
+
+int havoc_mi355x_cqt_decide(havoc_mi355x_ctx *ctx, int width, int height, int ctb_log2, int min_cb_log2, int flags, const uint8_t *d_cu_syntax,
+                            const int32_t *d_node_cu, const havoc_mi355x_cu_choice *d_choice, int n_choice, void *d_work, size_t work_bytes,
+                            havoc_mi355x_cqt_ctu *d_ctu, havoc_mi355x_cqt_node *d_node, int8_t *d_depth, uint8_t *d_cu_syntax_out)
+{
+    REQUIRE_CTX();
+    REQUIRE(ctb_log2 >= 4 && ctb_log2 <= 6, "cqt_decide: ctb_log2 must be 4..6");
+    REQUIRE(min_cb_log2 >= 3 && min_cb_log2 <= ctb_log2, "cqt_decide: min_cb_log2 must be 3..ctb_log2");
+    REQUIRE(width > 0 && height > 0 && width % (1 << min_cb_log2) == 0 && height % (1 << min_cb_log2) == 0,
+            "cqt_decide: width and height must be positive multiples of the minimum coding block size");
+    REQUIRE((flags & ~(HAVOC_CQT_WPP | HAVOC_CQT_ECU)) == 0, "cqt_decide: flags = HAVOC_CQT_WPP | HAVOC_CQT_ECU");
+    REQUIRE(n_choice >= 0, "cqt_decide: n_choice < 0");
+    REQUIRE(d_cu_syntax && d_node_cu && d_choice && d_work && d_ctu && d_node && d_depth && d_cu_syntax_out, "cqt_decide: null device pointer");
+    const long long n = (long long)((width + (1 << ctb_log2) - 1) >> ctb_log2) * ((height + (1 << ctb_log2) - 1) >> ctb_log2);
+    REQUIRE(n <= (1 << 24), "cqt_decide: too many CTUs");
+    REQUIRE(work_bytes >= cqt_decide_workspace_bytes((int)n) && (reinterpret_cast<uintptr_t>(d_work) & 7) == 0,
+            "cqt_decide: workspace misaligned or smaller than havoc_mi355x_cqt_decide_workspace(n_ctus)");
+    const void *ins[] = {d_cu_syntax, d_node_cu, d_choice};
+    const void *outs[] = {d_work, d_ctu, d_node, d_depth, d_cu_syntax_out};
+    uintptr_t bits = 0;
+    for (int a = 0; a < 5; ++a)
+    {
+        bits |= reinterpret_cast<uintptr_t>(outs[a]);
+        for (const void *i : ins) REQUIRE(outs[a] != i, "cqt_decide: an output must not be one of the inputs (which are never written)");
+        for (int b = 0; b < a; ++b) REQUIRE(outs[a] != outs[b], "cqt_decide: the outputs and the workspace must be distinct");
+    }
+    for (const void *i : ins) bits |= reinterpret_cast<uintptr_t>(i);
+    REQUIRE((bits & 7) == 0, "cqt_decide: every device pointer must be 8-byte aligned");
+    return check(launch_cqt_decide(LS(ctx), width, height, ctb_log2, min_cb_log2, flags, d_cu_syntax, d_node_cu, d_choice, n_choice, d_work, d_ctu, d_node, d_depth,
+                                   d_cu_syntax_out), "cqt_decide");
 }
 
 } // extern "C"

@@ -462,8 +462,14 @@ class DecisionPicture:
     PAD = 96
 
     def __init__(self, hv, width, height, bit_depth=8, qp=32, seed=11, threads=16, frames=None, density=1.0, intra=True, search_on_device=True, distance=1,
-                 sao=False, residual_rates=False, tree_rates=False, pu_modes=False, cu_close=False):
+                 sao=False, residual_rates=False, tree_rates=False, pu_modes=False, cu_close=False, cqt=False):
         import torch
+        if cqt and not search_on_device:
+            raise ValueError("cqt=True needs the device route (search_on_device=True)")
+        if cqt and not cu_close:
+            raise ValueError("cqt=True decides the coding quadtree over closed coding units: it needs cu_close=True")
+        if cqt and (width % 8 or height % 8):
+            raise ValueError("cqt=True needs a width and a height that are multiples of the minimum coding block size, 8")
         if cu_close and not search_on_device:
             raise ValueError("cu_close=True needs the device route (search_on_device=True)")
         if cu_close and not (tree_rates and pu_modes):
@@ -489,6 +495,8 @@ class DecisionPicture:
         self.pu_modes = pu_modes
         # every transform-tree unit closed as the reference closes an inter coding unit: the CU's own bits and the residual / no-residual decision (havoc_mi355x_cu_close)
         self.cu_close = cu_close
+        # every CTU's coding quadtree decided over those closed units: split_cu_flag's bits and the full / split comparison, CTU after CTU (havoc_mi355x_cqt_decide)
+        self.cqt = cqt
         self.sao = sao                                # in-loop SAO between deblocking and padding (sao_filter_inputs / sao_loop_filter)
         from . import havoc as hmod
         from . import workload
@@ -896,6 +904,56 @@ class DecisionPicture:
                                       pu_syntax=hv.down(Q["d_pu_after"], np.uint8).reshape(-1, hmod.PU_SYNTAX_CTX_BYTES),
                                       pred_ssd=hv.down(Q["d_pred_ssd"], np.int32).reshape(-1, 3), jobs=Q["jobs"], searched=Q["match"])
         return self._cu_decisions
+
+    # ---- the coding quadtree of every CTU over the closed units (Search<coding_quadtree>::go, turing/Search.hpp:808-886) ---------------------------------------
+    CQT_CTB_LOG2, CQT_MIN_CB_LOG2 = 6, 3
+
+    def _cqt_plan(self):
+        """cqt_decide's node table and buffers, built once from self.units: a unit of size 2^L at (x, y) is the node of its CTU at depth 6 - L (index (4^d - 1) / 3 +
+        the z-order index of its place); every other node is -1.  The slice's initial snapshot is CTU 0's of cu_syntax_states."""
+        if hasattr(self, "cqt_plan"):
+            return self.cqt_plan
+        hv, torch, hmod = self.hv, self.torch, self.hmod
+        ctb, mcb = self.CQT_CTB_LOG2, self.CQT_MIN_CB_LOG2
+        u, nodes = self.units, hmod.cqt_nodes(ctb, mcb)
+        x, y, l = u["x0"].astype(np.int64), u["y0"].astype(np.int64), u["log2_size"].astype(np.int64)
+        d = ctb - l
+        assert (d >= 0).all() and (d <= ctb - mcb).all() and self.cx == -(-self.W >> ctb) and self.cy == -(-self.H >> ctb)
+        px, py = (x & 63) >> l, (y & 63) >> l
+        z = np.zeros(len(u), np.int64)
+        for b in range(ctb - mcb):
+            z |= (px >> b & 1) << (2 * b) | (py >> b & 1) << (2 * b + 1)
+        node_cu = np.full((self.cx * self.cy, nodes), -1, np.int32)
+        node_cu[(y >> ctb) * self.cx + (x >> ctb), (4 ** d - 1) // 3 + z] = np.arange(len(u))
+        with torch.cuda.stream(hv.tstream):
+            d_node_cu = torch.from_numpy(node_cu.reshape(-1).copy()).to(hv.device)
+        self.cqt_plan = dict(node_cu=node_cu, d_node_cu=d_node_cu, **hv.cqt_buffers(self.W, self.H, ctb, mcb))
+        return self.cqt_plan
+
+    def cqt_launch(self):
+        """the coding quadtree of every CTU over the records cu_close_launches() left on the device, WPP on, ecu off.  One call; asynchronous"""
+        hv, Q, B = self.hv, self._cu_plan(), self._cqt_plan()
+        hv.cqt_decide_d(self.W, self.H, self.CQT_CTB_LOG2, self.CQT_MIN_CB_LOG2, self.hmod.CQT_WPP, self.d_cu_syntax_states, B["d_node_cu"], Q["d_out"], B["work"],
+                        B["ctu"], B["node"], B["depth"], B["cu_syntax_out"])
+
+    @property
+    def cqt_decisions(self):
+        """what cqt_launch() left on the device, as numpy: dict(ctus (havoc.CQT_CTU_DT [CTUs]), nodes (CQT_NODE_DT [CTUs, 85]), depth (int8 [8 cy, 8 cx]: CtDepth per
+        8x8 cell, whole CTUs, 0 outside the picture), cu_syntax (uint8 [CTUs, 16]: the snapshot after each CTU), node_cu (int32 [CTUs, 85] as uploaded), gave_up (a wait
+        on the row above gave up: every record then has decided = 0 and nothing is to be used)).
+        The limit today: only the units that have a transform tree have a closed coding unit -- 32x32, and 16x16 / 8x8 along a partial edge -- so every 64x64 node is
+        without a candidate and splits, every 32x32 unit stands without a comparison (no node below it has a candidate), a unit whose record cu_close refused refuses
+        its CTU (decided = 0), and no full-against-split comparison is live until
+        trees exist at every searched size.  What a picture does exercise: the forced splits and deleted quadtrees of a partial last row and column, the depth map,
+        and the context chain over real rows."""
+        if not self.cqt:
+            raise ValueError("cqt_decisions: the picture was made without cqt=True")
+        if getattr(self, "_cqt_decisions", None) is None:
+            B = self._cqt_plan()
+            work = self.hv.down(B["work"], np.int64)        # [CTUs]: the published words; then the row ticket (low half) and the give-up word (high half)
+            self._cqt_decisions = dict(node_cu=B["node_cu"], gave_up=bool(work[self.cx * self.cy] >> 32),
+                                       **self.hv.cqt_download(B, self.W, self.H, self.CQT_CTB_LOG2, self.CQT_MIN_CB_LOG2))
+        return self._cqt_decisions
 
     def chroma_chain(self, field):
         """the inter residual of the chroma planes at the decided vectors (turing/Reconstruct.cpp:1274-1286 with cIdx 1, 2): HavocPredUni 4-tap of every unit's
@@ -1400,9 +1458,10 @@ class DecisionPicture:
         if self.search_on_device:
             # everything after the searches is a FIXED sequence of launches over device-resident tables (the decided field never leaves the device, the decisions
             # between the launches are kernels): recorded once into a HIP graph, one launch per picture, one wait at the end
-            self._rqt = self._cells = self._sao_decisions = self._rqt_rates = self._rqt_tree = self._cu_decisions = None
+            self._rqt = self._cells = self._sao_decisions = self._rqt_rates = self._rqt_tree = self._cu_decisions = self._cqt_decisions = None
             pu = (self.pu_mode_launches,) if self.pu_modes else ()      # (the tables its launches read went up before the replay: pu_candidates)
             pu += (self.cu_close_launches,) if self.cu_close else ()     # (after the tree decisions AND the prediction units' rates: it reads both in place)
+            pu += (self.cqt_launch,) if self.cqt else ()                 # (behind cu_close: it reads its records in place)
             if self.sao:
                 self._replayed("after the searches", lambda: (self.merge_candidates(field), self.predict(field), self.sao_filter_inputs(field),
                                                               self.sao_loop_filter(), [f() for f in pu]))
@@ -1474,6 +1533,8 @@ class DecisionPicture:
             raise ValueError("step_banded does not decide the prediction units' modes: use step() with pu_modes=True")
         if self.cu_close:
             raise ValueError("step_banded does not close coding units: use step() with cu_close=True")
+        if self.cqt:
+            raise ValueError("step_banded does not decide coding quadtrees: use step() with cqt=True")
         if self.sao:
             # SAO of band b reads the deblocked rows of band b + 1 (turing/TaskSao.cpp:46-56): not built
             raise ValueError("step_banded does not run SAO: use step() with sao=True")
@@ -1555,7 +1616,7 @@ class DecisionPicture:
 
     def results(self):
         """what the TU chain left on the device, as numpy (per group): coefficients, levels, flags, SSDs; and the reconstruction; with pu_modes=True a third entry,
-        dict(pu_modes=self.pu_decisions), with cu_close=True also cu_close=self.cu_decisions"""
+        dict(pu_modes=self.pu_decisions), with cu_close=True also cu_close=self.cu_decisions, with cqt=True also cqt=self.cqt_decisions"""
         hv = self.hv
         out = [dict(log2=g["log2"], coef=hv.down(g["coef"], np.int16), level=hv.down(g["level"], np.int16), cbf=hv.down(g["cbf"], np.int32),
                     ssd=hv.down(g["ssd"], np.uint32)) for g in self.groups]
@@ -1563,5 +1624,7 @@ class DecisionPicture:
             extra = dict(pu_modes=self.pu_decisions)
             if self.cu_close:
                 extra["cu_close"] = self.cu_decisions
+            if self.cqt:
+                extra["cqt"] = self.cqt_decisions
             return out, hv.down(self.recon, self.dt), extra
         return out, hv.down(self.recon, self.dt)

@@ -135,6 +135,7 @@ def _load():
         "pu_decide": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp],
         "cu_close": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_int32, _vp, _vp, _vp],
         "unit_pred_ssd": [_vp, _i, _vp, C.c_ssize_t, _vp, C.c_ssize_t, _vp, C.c_ssize_t, _vp, C.c_ssize_t, _vp, _i, _vp],
+        "cqt_decide": [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, C.c_size_t, _vp, _vp, _vp, _vp],
         "intra_decide_rated": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_int32, _vp, _vp],
         "rqt_decide_rated": [_vp, _vp, _i, _vp, _vp, _vp, _vp, C.c_int64, C.c_ssize_t, _i, _i, _vp],
         "rqt_decide_tree": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_ssize_t, _i, C.c_int64, C.c_int64, C.c_ssize_t, _i, _i, _vp, _vp],
@@ -154,6 +155,8 @@ def _load():
     L.havoc_mi355x_sao_workspace.restype = C.c_size_t
     L.havoc_mi355x_sao_decide_workspace.argtypes = [_i]
     L.havoc_mi355x_sao_decide_workspace.restype = C.c_size_t
+    L.havoc_mi355x_cqt_decide_workspace.argtypes = [_i]
+    L.havoc_mi355x_cqt_decide_workspace.restype = C.c_size_t
     L.havoc_mi355x_search_workspace.argtypes = [_i, _i]
     L.havoc_mi355x_search_workspace.restype = C.c_size_t
     for name, args in sig.items():
@@ -167,7 +170,8 @@ def exported_symbols():
     """names the C ABI must export (checked against include/havoc_mi355x.h by the CPU tests)"""
     _, names = _load()
     return ["havoc_mi355x_" + n for n in names] + ["havoc_mi355x_last_error", "havoc_mi355x_version", "havoc_mi355x_rdoq_lambda", "havoc_mi355x_rdoq_workspace",
-                                                "havoc_mi355x_search_workspace", "havoc_mi355x_sao_workspace", "havoc_mi355x_sao_decide_workspace"]
+                                                "havoc_mi355x_search_workspace", "havoc_mi355x_sao_workspace", "havoc_mi355x_sao_decide_workspace",
+                                                "havoc_mi355x_cqt_decide_workspace"]
 
 
 # one havoc_mi355x_cell (include/havoc_mi355x.h), 16 bytes: a 4x4 luma cell of a picture's block structure
@@ -344,6 +348,20 @@ assert CU_CLOSE_JOB_DT.itemsize == 32 and CU_CHOICE_DT.itemsize == 48 and PRED_S
 CU_CLOSE_MIN_CB, CU_CLOSE_AMP, CU_CLOSE_MERGE_2Nx2N = 1, 2, 4
 CU_OUTCOME_REFUSED, CU_OUTCOME_CODED, CU_OUTCOME_NO_RESIDUAL, CU_OUTCOME_SKIPPED = -1, 0, 1, 2
 CU_SYNTAX_CTX_BYTES = 16        # HAVOC_CU_SYNTAX_CTX_*: split_cu_flag[3], cu_skip_flag[3], pred_mode_flag, part_mode[4], rqt_root_cbf, 4 reserved
+# one havoc_mi355x_cqt_ctu / havoc_mi355x_cqt_node (include/havoc_mi355x.h): a CTU's decided coding quadtree, one node of it
+CQT_CTU_DT = np.dtype([("decided", "<i4"), ("n_cus", "<i4"), ("rate", "<i8"), ("flag_rate", "<i8"), ("lambda_distortion", "<i8"), ("cost", "<i8")])
+CQT_NODE_DT = np.dtype([("choice", "u1"), ("flags", "u1"), ("ctx_inc", "u1"), ("pad", "u1", 5), ("cost_full", "<i8"), ("cost_split", "<i8")])
+assert CQT_CTU_DT.itemsize == 40 and CQT_NODE_DT.itemsize == 24
+CQT_WPP, CQT_ECU = 1, 2
+CQT_NOT_VISITED, CQT_CU, CQT_SPLIT, CQT_DELETED = 0, 1, 2, 3
+CQT_NODE_FINAL, CQT_NODE_FLAG_CODED, CQT_NODE_MUST_SPLIT, CQT_NODE_ECU_STOP, CQT_NODE_NO_CANDIDATE, CQT_NODE_NO_SPLIT_CANDIDATE = 1, 2, 4, 8, 16, 32
+
+
+def cqt_nodes(ctb_log2, min_cb_log2):
+    """nodes of a CTU's coding quadtree: 1 + 4 + ... + 4^(ctb_log2 - min_cb_log2); node (d, z) has index (4^d - 1) / 3 + z"""
+    return (4 ** (ctb_log2 - min_cb_log2 + 1) - 1) // 3
+
+
 # havoc_mi355x_rqt_chroma_at / havoc_mi355x_rqt_tree_choice (include/havoc_mi355x.h), 16 bytes each: where a unit's chroma candidates are / what rqt_decide_tree adds
 RQT_CHROMA_AT_DT = np.dtype([("cb_zero", "<i4"), ("cr_zero", "<i4"), ("cb_one", "<i4"), ("cr_one", "<i4")])
 RQT_TREE_RESULT_DT = np.dtype([("mask_zero", "<u4"), ("mask_one", "<u4"), ("chroma_ssd_zero", "<i4"), ("chroma_ssd_one", "<i4")])
@@ -1050,6 +1068,47 @@ class Havoc:
             pu_out = t.zeros(max(n, 1) * 16, dtype=t.uint8, device=self.device)
         self._ck(self.L.havoc_mi355x_cu_close(self.h, *[_ptr(a) for a in ins], _ptr(j), n, int(max_num_merge_cand), int(lam_q16), _ptr(out), _ptr(cu_out), _ptr(pu_out)))
         return (self.down(out, np.uint8)[:n * 48].view(CU_CHOICE_DT).copy(), self.down(cu_out, np.uint8)[:n * 16].reshape(-1, 16), self.down(pu_out, np.uint8)[:n * 16].reshape(-1, 16))
+
+    def cqt_decide_workspace(self, n_ctus):
+        """device scratch for one cqt_decide call over `n_ctus` CTUs (an int64 tensor: 8-byte aligned); the call resets it itself"""
+        n = int(self.L.havoc_mi355x_cqt_decide_workspace(int(n_ctus)))
+        with self.torch.cuda.stream(self.tstream):
+            return self.torch.zeros((n + 7) // 8, dtype=self.torch.int64, device=self.device)
+
+    def cqt_decide_d(self, width, height, ctb_log2, min_cb_log2, flags, cu_syntax, node_cu, choice, work, ctu, node, depth, cu_syntax_out):
+        """the coding quadtree of every CTU (havoc_mi355x_cqt_decide) over cu_close's records, read in place: cu_syntax uint8 [16] (the slice's initial snapshot),
+        node_cu int32 [n_ctus * cqt_nodes] (the index in `choice` of each node's candidate, -1: none), choice: uint8 tensor of CU_CHOICE_DT; outputs: uint8 tensors of
+        CQT_CTU_DT [n_ctus] and CQT_NODE_DT [n_ctus * cqt_nodes], the CtDepth map int8 (whole CTUs, a byte per MinCb cell), the snapshots uint8 [n_ctus * 16].  No sync."""
+        self._ck(self.L.havoc_mi355x_cqt_decide(self.h, int(width), int(height), int(ctb_log2), int(min_cb_log2), int(flags), _ptr(cu_syntax), _ptr(node_cu), _ptr(choice),
+                                                choice.numel() * choice.element_size() // CU_CHOICE_DT.itemsize, _ptr(work), work.numel() * work.element_size(),
+                                                _ptr(ctu), _ptr(node), _ptr(depth), _ptr(cu_syntax_out)))
+
+    def cqt_buffers(self, width, height, ctb_log2, min_cb_log2):
+        """-> dict(work, ctu, node, depth, cu_syntax_out): the workspace and zeroed outputs of cqt_decide_d for a picture"""
+        t = self.torch
+        cx, cy, cells = -(-width >> ctb_log2), -(-height >> ctb_log2), 1 << (ctb_log2 - min_cb_log2)
+        n, nodes = cx * cy, cqt_nodes(ctb_log2, min_cb_log2)
+        with t.cuda.stream(self.tstream):
+            z = lambda k: t.zeros(k, dtype=t.uint8, device=self.device)
+            return dict(work=self.cqt_decide_workspace(n), ctu=z(n * CQT_CTU_DT.itemsize), node=z(n * nodes * CQT_NODE_DT.itemsize),
+                        depth=t.zeros(n * cells * cells, dtype=t.int8, device=self.device), cu_syntax_out=z(n * CU_SYNTAX_CTX_BYTES))
+
+    def cqt_download(self, B, width, height, ctb_log2, min_cb_log2):
+        """the outputs in cqt_buffers' dict as numpy: dict(ctus CQT_CTU_DT [n], nodes CQT_NODE_DT [n, cqt_nodes], depth int8 [rows, cells per row], cu_syntax [n, 16])"""
+        cx, cy, cells = -(-width >> ctb_log2), -(-height >> ctb_log2), 1 << (ctb_log2 - min_cb_log2)
+        return dict(ctus=self.down(B["ctu"], np.uint8).view(CQT_CTU_DT).copy(),
+                    nodes=self.down(B["node"], np.uint8).view(CQT_NODE_DT).reshape(cx * cy, cqt_nodes(ctb_log2, min_cb_log2)).copy(),
+                    depth=self.down(B["depth"], np.int8).reshape(cy * cells, cx * cells), cu_syntax=self.down(B["cu_syntax_out"], np.uint8).reshape(-1, CU_SYNTAX_CTX_BYTES))
+
+    def cqt_decide(self, width, height, ctb_log2, min_cb_log2, flags, cu_syntax, node_cu, choice):
+        """numpy level: cu_syntax uint8 [16], node_cu int32 [n_ctus, cqt_nodes], choice CU_CHOICE_DT [m] -> cqt_download's dict"""
+        t = self.torch
+        with t.cuda.stream(self.tstream):
+            up = lambda a: t.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(self.device) if np.size(a) else t.zeros(64, dtype=t.uint8, device=self.device)
+            ins = [up(np.asarray(cu_syntax, np.uint8)), up(np.asarray(node_cu, np.int32)), up(np.ascontiguousarray(choice, CU_CHOICE_DT))]
+        B = self.cqt_buffers(width, height, ctb_log2, min_cb_log2)
+        self.cqt_decide_d(width, height, ctb_log2, min_cb_log2, flags, ins[0], ins[1], ins[2], B["work"], B["ctu"], B["node"], B["depth"], B["cu_syntax_out"])
+        return self.cqt_download(B, width, height, ctb_log2, min_cb_log2)
 
     def unit_pred_ssd_d(self, bit_depth, src_y, src_stride, src_c, src_stride_c, pred_y, pred_stride, pred_c, pred_stride_c, jobs, out):
         """SSD(source, prediction) of units' luma, Cb and Cr blocks in one launch (havoc_mi355x_unit_pred_ssd); jobs: uint8 tensor of PRED_SSD_JOB_DT; out: int32 [3 n].
