@@ -733,7 +733,7 @@ int havoc_mi355x_intra_rate(havoc_mi355x_ctx *ctx, int log2TrafoSize, const int1
 
 /* ---- the CABAC rate of an inter unit's whole transform tree at one depth (csrc/kernels_residual_rate.hip: k_tree_rate) ----
  * What the inter transform-tree decision compares (turing/Reconstruct.cpp:1296-1428): EstimateRate<void> over `if (rqt_root_cbf) transform_tree` of an inter 2Nx2N coding
- * unit of log2 size L = log2CbSize in {3, 4, 5}, coded at `depth` 0 (one transform unit) or 1 (four), with ONE CABAC state running through split_transform_flag, cbf_cb,
+ * unit of log2 size L = log2CbSize in {3, 4, 5} (6: below), coded at `depth` 0 (one transform unit) or 1 (four), with ONE CABAC state running through split_transform_flag, cbf_cb,
  * cbf_cr, cbf_luma and the Y, Cb and Cr residual_coding (Syntax<transform_tree>, turing/SyntaxCtu.hpp:329-379; Syntax<transform_unit>, :411-502; the writers,
  * turing/Binarization.h:617-666).  rqt_root_cbf itself is NOT priced.  Preconditions (turing/Encoder.cpp:662-666 with the residual quadtree on): MaxTrafoDepth 1 for
  * inter, MinTbLog2SizeY 2, MaxTbLog2SizeY >= L, 4:2:0, CuPredMode MODE_INTER, scanIdx 0, and cu_qp_delta_enabled_flag, cu_chroma_qp_offset_enabled_flag,
@@ -748,11 +748,15 @@ int havoc_mi355x_intra_rate(havoc_mi355x_ctx *ctx, int log2TrafoSize, const int1
  * (HAVOC_INTRA_SYNTAX_CTX_SPLIT_TRANSFORM_FLAG; its first byte passes through), everything else in the 128-byte one.
  * d_rate[out_index]: the Q16 Cost.  d_cbf[out_index]: bit k = Y block k has a level, bit 4 + k = Cb block k, bit 8 + k = Cr block k (depth 0, and the chroma of L == 3, use
  * k = 0 only).  d_states_out / d_syntax_states_out: NULL, or njobs x 128 / njobs x 4 bytes: job j's snapshots as its walk left them (an all-zero tree: its input).
+ * (6, 1) is accepted as well: a 64x64 unit lies above MaxTbLog2SizeY (5), so its transform depth and its split are inferred (turing/Reconstruct.cpp:1300-1310) and it has ONE
+ * tree -- depth 1 as above WITHOUT the split_transform_flag bin: cbf_cb, cbf_cr (ctxInc 0), then per child cbf_cb / cbf_cr (ctxInc 1, only when the parent's is 1),
+ * cbf_luma (ctxInc 0), Y 32x32, Cb and Cr 16x16.  (6, 0) does not exist.
  * For L in {3, 4, 5} the syntax can code split_transform_flag at every size, so no flag value is impossible; a job whose `flags` has a bit other than
- * HAVOC_TREE_RATE_SPLIT_FLAG_CODED cannot be walked: no level of it is read, d_rate = -1, d_cbf = 0, its output snapshots are its input.  The flag itself is TRUSTED: the
+ * HAVOC_TREE_RATE_SPLIT_FLAG_CODED cannot be walked: no level of it is read, d_rate = -1, d_cbf = 0, its output snapshots are its input.  For L == 6 the flag is never
+ * coded: HAVOC_TREE_RATE_SPLIT_FLAG_CODED is an impossible value there and is refused in the same way, like an unknown bit.  Below 6 the flag itself is TRUSTED: the
  * kernel sees neither MaxTbLog2SizeY nor MaxTrafoDepth, so a caller who sets it for a unit whose split is inferred (a 32x32 unit above MaxTbLog2SizeY, interSplitFlag) gets
  * the price of a bin the syntax does not code, and no refusal.  The offsets and indices are trusted: luma_off, cb_off and cr_off are multiples of 4 (the levels are read
- * as 8-byte rows).  The inputs are never written.  d_luma_levels, d_chroma_levels and d_rate 8-byte aligned, d_cbf 4-byte.  EINVAL: log2CbSize outside 3..5, depth outside 0..1,
+ * as 8-byte rows).  The inputs are never written.  d_luma_levels, d_chroma_levels and d_rate 8-byte aligned, d_cbf 4-byte.  EINVAL: log2CbSize outside 3..6, depth outside 0..1, log2CbSize 6 at depth 0,
  * njobs < 0, a null input or d_rate / d_cbf, an output snapshot table that is its input.  No allocation, no synchronisation, no workspace: capturable into a HIP graph. */
 enum { HAVOC_TREE_RATE_SPLIT_FLAG_CODED = 1 };   /* split_transform_flag of the unit is coded (as `depth`) */
 typedef struct {
@@ -957,6 +961,22 @@ int havoc_mi355x_rqt_decide_tree(havoc_mi355x_ctx *ctx, const havoc_mi355x_rqt_u
                                  const int64_t *d_tree_rate, const uint32_t *d_tree_cbf, int64_t rec_origin, intptr_t rec_stride, int32_t dump_off,
                                  int64_t cb_origin, int64_t cr_origin, intptr_t c_stride, int32_t c_dump_off, int32_t reciprocal_lambda_q16,
                                  havoc_mi355x_rqt_choice *d_out, havoc_mi355x_rqt_tree_choice *d_tree_out);
+/* The same decision for units that OVERLAP one another -- the searched 2Nx2N units of every size of a coding quadtree, each with the tree of its own prediction -- which
+ * cannot all be reconstructed into one picture: which of them are is the quadtree's decision.  It writes NO final job record and takes no reconstruction argument:
+ * sizes[k].d_final, d_jobs and d_stats (and csizes') may be NULL and are never touched.  For units of log2_size 3..5 d_out and d_tree_out are
+ * havoc_mi355x_rqt_decide_tree's on the same tables, byte for byte.  log2_size 6 is accepted: a 64x64 unit lies above MaxTbLog2SizeY, its split is inferred
+ * (turing/Reconstruct.cpp:1300-1310) and only its depth-1 candidates exist -- four 32x32 luma blocks at d_one_at[i] .. + 3 of sizes[3], four Cb and four Cr 16x16 blocks at
+ * cb_one / cr_one .. + 3 of csizes[2], the rate and mask at d_tree_rate / d_tree_cbf [2 i + 1] (havoc_mi355x_tree_rate at (6, 1)); d_zero_at[i], cb_zero, cr_zero and
+ * entry 2 i are not read.  Its record: one[], cost_one, mask_one and chroma_ssd_one as for any unit; tried_zero = 0 and the zero fields 0, as an untried depth 0 is
+ * recorded; depth = 1 when mask_one != 0, else 0 -- the "unsplit without residual" record.  (The reference calls this tree rqtdepth 0; it is recorded as the depth that
+ * is coded, so that havoc_mi355x_cu_close's d = (depth == 0 && tried_zero) ? 0 : 1 reads the right tree.)  A unit of another size: depth = -1, nothing else.
+ * The tables, offsets and indices are trusted; the inputs are never written.  EINVAL: n < 0; null sizes / csizes; with n > 0 a null d_units, d_zero_at, d_one_at,
+ * d_chroma_at, d_tree_rate, d_tree_cbf, d_out or d_tree_out; a negative reciprocal_lambda_q16; a size table with one of d_cbf / d_ssd and not the other.  No allocation,
+ * no synchronisation, no workspace: capturable into a HIP graph. */
+int havoc_mi355x_rqt_decide_units(havoc_mi355x_ctx *ctx, const havoc_mi355x_rqt_unit *d_units, int n, const int32_t *d_zero_at, const int32_t *d_one_at,
+                                  const havoc_mi355x_rqt_size sizes[4], const havoc_mi355x_rqt_size csizes[4], const havoc_mi355x_rqt_chroma_at *d_chroma_at,
+                                  const int64_t *d_tree_rate, const uint32_t *d_tree_cbf, int32_t reciprocal_lambda_q16, havoc_mi355x_rqt_choice *d_out,
+                                  havoc_mi355x_rqt_tree_choice *d_tree_out);
 /* the 4x4 cells havoc_mi355x_derive_bs reads, made from the decisions: every unit one inter 2Nx2N prediction unit from list 0 (decoded picture dpb_index0) at the vector d_field
  * (int16 [2][height / 4][width / 4][2]) holds at its origin, coded flags and transform sizes as decided; cells outside the units: no motion coded, qp, tu_log2 = 2 */
 int havoc_mi355x_block_cells(havoc_mi355x_ctx *ctx, int width, int height, int qp, int dpb_index0, const int16_t *d_field, const havoc_mi355x_rqt_unit *d_units,
@@ -1053,6 +1073,23 @@ typedef struct { int32_t src_off[3], pred_off[3], log2_size, reserved; } havoc_m
 int havoc_mi355x_unit_pred_ssd(havoc_mi355x_ctx *ctx, int bit_depth, const void *d_src_y, intptr_t src_stride, const void *d_src_c, intptr_t src_stride_c,
                                const void *d_pred_y, intptr_t pred_stride, const void *d_pred_c, intptr_t pred_stride_c, const havoc_mi355x_pred_ssd_job *d_jobs, int n,
                                int32_t *d_out);
+/* The winner's prediction of n searched units in one launch: what go2 leaves behind for reconstructInter (turing/Search.hpp:1829-1842, then :2362-2568 on that
+ * prediction).  havoc_mi355x_pu_decide leaves unit u's winner in d_best[u] (0, 1, 2: the first, second, third candidate of the unit -- L0, L1, bi; -1: none), and the
+ * candidates' predictions lie as contiguous blocks, candidate k of a unit (1 << 2 * log2) samples behind candidate k - 1 in each plane (log2 = log2_size in luma,
+ * log2_size - 1 in Cb and Cr).  Per job: the winner's Y block from d_cand_y + cand_off[0] + (best << 2 log2_size) to d_dst_y + dst_off[0] (rows dst_stride apart), its
+ * Cb and Cr blocks from d_cand_c + cand_off[1], [2] + (best << 2 (log2_size - 1)) to d_dst_c + dst_off[1], [2] (rows dst_stride_c apart); offsets and strides in
+ * samples of 1 (bit_depth 8) or 2 bytes.  d_unit_cand[unit] = d_first[unit] + best, d_unit_rate[unit] = d_rate[that candidate] (havoc_mi355x_pu_rate's): what
+ * havoc_mi355x_cu_close charges as the unit's PU rate.  A unit without a winner (best < 0, or a value above 2, which pu_decide does not write for three candidates):
+ * d_unit_rate = d_unit_cand = -1 and NOTHING of it is copied.  log2_size 3..6, sizes mixed freely; destination blocks of different jobs must not overlap.
+ * Alignment: none is required of offsets or strides (rows move in unaligned 8-byte pieces, 4-byte pieces for an 8-bit 4x4 chroma block); a caller who keeps every
+ * block and plane at a multiple of 8 bytes -- a picture width that is a multiple of 8 with blocks at their picture positions does -- gets one aligned access per
+ * piece.  The records are trusted: offsets, log2_size and unit are not checked. */
+typedef struct { int32_t cand_off[3], dst_off[3], log2_size, unit; } havoc_mi355x_pred_select_job;     /* sizeof: 32 */
+/* The inputs are never written.  EINVAL: a null pointer, n < 0, a bit depth outside 8..16, a stride that is not positive, d_rate or d_unit_rate not 8-byte aligned, an
+ * output that is an input or another output.  No allocation, no synchronisation, no workspace: capturable into a HIP graph. */
+int havoc_mi355x_unit_pred_select(havoc_mi355x_ctx *ctx, int bit_depth, const void *d_cand_y, const void *d_cand_c, void *d_dst_y, intptr_t dst_stride, void *d_dst_c,
+                                  intptr_t dst_stride_c, const int32_t *d_first, const int32_t *d_best, const int64_t *d_rate, const havoc_mi355x_pred_select_job *d_jobs,
+                                  int n, int64_t *d_unit_rate, int32_t *d_unit_cand);
 
 /* ---- the coding quadtree of every CTU: split_cu_flag's bits and the full / split decision (csrc/kernels_cqt.hip: k_cqt_decide) ----
  * Search<coding_quadtree>::go (turing/Search.hpp:709-887, the decision :808-886) over Syntax<coding_quadtree>::go (turing/SyntaxCtu.hpp:95-139) and the writer of

@@ -37,6 +37,7 @@ static_assert(sizeof(havoc_mi355x_cqt_ctu) == 40 && offsetof(havoc_mi355x_cqt_ct
               offsetof(havoc_mi355x_cqt_node, cost_full) == 8 && offsetof(havoc_mi355x_cu_choice, lambda_distortion) == 16, "the coding-quadtree records are ABI");
 static_assert(sizeof(havoc_mi355x_intra_rate_job) == 32 && offsetof(havoc_mi355x_intra_rate_job, scan_idx) == 12 && offsetof(havoc_mi355x_intra_rate_job, flags) == 15,
               "job ABI");
+static_assert(sizeof(havoc_mi355x_pred_select_job) == 32 && offsetof(havoc_mi355x_pred_select_job, log2_size) == 24, "job ABI");
 static_assert(sizeof(havoc_mi355x_tree_rate_job) == 32 && offsetof(havoc_mi355x_tree_rate_job, out_index) == 16 && offsetof(havoc_mi355x_tree_rate_job, flags) == 21, "job ABI");
 static_assert(sizeof(havoc_mi355x_intra_mpm) == 40 && sizeof(havoc_mi355x_intra_choice) == 40, "job ABI");
 static_assert(sizeof(havoc_mi355x_rdoq_job) == 48 && offsetof(havoc_mi355x_rdoq_job, c_idx) == 32, "job ABI");
@@ -764,6 +765,25 @@ int havoc_mi355x_rqt_decide_tree(havoc_mi355x_ctx *ctx, const havoc_mi355x_rqt_u
                                         (long)cb_origin, (long)cr_origin, (int)c_stride, c_dump_off, reciprocal_lambda_q16, d_out, d_tree_out), "rqt_decide_tree");
 }
 
+int havoc_mi355x_rqt_decide_units(havoc_mi355x_ctx *ctx, const havoc_mi355x_rqt_unit *d_units, int n, const int32_t *d_zero_at, const int32_t *d_one_at,
+                                  const havoc_mi355x_rqt_size sizes[4], const havoc_mi355x_rqt_size csizes[4], const havoc_mi355x_rqt_chroma_at *d_chroma_at,
+                                  const int64_t *d_tree_rate, const uint32_t *d_tree_cbf, int32_t reciprocal_lambda_q16, havoc_mi355x_rqt_choice *d_out,
+                                  havoc_mi355x_rqt_tree_choice *d_tree_out)
+{
+    REQUIRE_CTX(); REQUIRE(n >= 0, "n < 0"); REQUIRE(sizes != nullptr && csizes != nullptr, "null sizes");
+    REQUIRE(n == 0 || (d_units && d_zero_at && d_one_at && d_chroma_at && d_tree_rate && d_tree_cbf && d_out && d_tree_out), "null device pointer");
+    REQUIRE(reciprocal_lambda_q16 >= 0, "reciprocal_lambda_q16 < 0");
+    if (n > 0)      // as havoc_mi355x_rqt_decide_tree, but only the outcomes are read: d_stats, d_jobs and d_final may be null; a table has its cbf and ssd or is absent
+        for (int k = 0; k < 4; ++k)
+        {
+            const havoc_mi355x_rqt_size &z = sizes[k], &c = csizes[k];
+            REQUIRE((z.d_cbf != nullptr) == (z.d_ssd != nullptr), "rqt_decide_units: a size table with some null pointers");
+            REQUIRE((c.d_cbf != nullptr) == (c.d_ssd != nullptr), "rqt_decide_units: a chroma size table with some null pointers");
+        }
+    return check(launch_rqt_decide_units(LS(ctx), d_units, n, d_zero_at, d_one_at, sizes, csizes, d_chroma_at, d_tree_rate, d_tree_cbf, reciprocal_lambda_q16, d_out, d_tree_out),
+                 "rqt_decide_units");
+}
+
 int havoc_mi355x_block_cells(havoc_mi355x_ctx *ctx, int width, int height, int qp, int dpb_index0, const int16_t *d_field, const havoc_mi355x_rqt_unit *d_units,
                              const havoc_mi355x_rqt_choice *d_decisions, int n, havoc_mi355x_cell *d_cells)
 {
@@ -1084,7 +1104,8 @@ int havoc_mi355x_tree_rate(havoc_mi355x_ctx *ctx, int log2CbSize, int depth, con
                            const uint8_t *d_syntax_states, const havoc_mi355x_tree_rate_job *d_jobs, int njobs, int64_t *d_rate, uint32_t *d_cbf,
                            uint8_t *d_states_out, uint8_t *d_syntax_states_out)
 {
-    REQUIRE_CTX(); REQUIRE(log2CbSize >= 3 && log2CbSize <= 5, "tree_rate: log2CbSize must be 3..5"); REQUIRE(depth == 0 || depth == 1, "tree_rate: depth must be 0 or 1");
+    REQUIRE_CTX(); REQUIRE(log2CbSize >= 3 && log2CbSize <= 6, "tree_rate: log2CbSize must be 3..6"); REQUIRE(depth == 0 || depth == 1, "tree_rate: depth must be 0 or 1");
+    REQUIRE(log2CbSize <= 5 || depth == 1, "tree_rate: log2CbSize 6 exists at depth 1 only (the split of a 64x64 unit is inferred)");
     REQUIRE(njobs >= 0, "njobs < 0");
     REQUIRE(d_luma_levels && d_chroma_levels && d_states && d_syntax_states && d_jobs && d_rate && d_cbf, "tree_rate: null device pointer");
     REQUIRE((reinterpret_cast<uintptr_t>(d_luma_levels) & 7) == 0 && (reinterpret_cast<uintptr_t>(d_chroma_levels) & 7) == 0 && (reinterpret_cast<uintptr_t>(d_rate) & 7) == 0 &&
@@ -1160,6 +1181,26 @@ int havoc_mi355x_unit_pred_ssd(havoc_mi355x_ctx *ctx, int bit_depth, const void 
     for (const void *i : {d_src_y, d_src_c, d_pred_y, d_pred_c, static_cast<const void *>(d_jobs)}) REQUIRE(i != d_out, "unit_pred_ssd: d_out must not be one of the inputs");
     return check(launch_unit_pred_ssd(LS(ctx), bit_depth == 8 ? 1 : 2, d_src_y, src_stride, d_src_c, src_stride_c, d_pred_y, pred_stride, d_pred_c, pred_stride_c, d_jobs, n,
                                       d_out), "unit_pred_ssd");
+}
+
+int havoc_mi355x_unit_pred_select(havoc_mi355x_ctx *ctx, int bit_depth, const void *d_cand_y, const void *d_cand_c, void *d_dst_y, intptr_t dst_stride, void *d_dst_c,
+                                  intptr_t dst_stride_c, const int32_t *d_first, const int32_t *d_best, const int64_t *d_rate, const havoc_mi355x_pred_select_job *d_jobs,
+                                  int n, int64_t *d_unit_rate, int32_t *d_unit_cand)
+{
+    REQUIRE_CTX(); REQUIRE(n >= 0, "n < 0"); REQUIRE(bit_depth >= 8 && bit_depth <= 16, "unit_pred_select: bit_depth must be 8..16");
+    REQUIRE(d_cand_y && d_cand_c && d_dst_y && d_dst_c && d_first && d_best && d_rate && d_jobs && d_unit_rate && d_unit_cand, "unit_pred_select: null device pointer");
+    REQUIRE(dst_stride > 0 && dst_stride_c > 0, "unit_pred_select: a stride must be positive");
+    REQUIRE((reinterpret_cast<uintptr_t>(d_rate) & 7) == 0 && (reinterpret_cast<uintptr_t>(d_unit_rate) & 7) == 0, "unit_pred_select: d_rate and d_unit_rate must be 8-byte aligned");
+    const void *outs[] = {d_dst_y, d_dst_c, d_unit_rate, d_unit_cand};
+    for (int a = 0; a < 4; ++a)
+    {
+        for (const void *i : {d_cand_y, d_cand_c, static_cast<const void *>(d_first), static_cast<const void *>(d_best), static_cast<const void *>(d_rate),
+                              static_cast<const void *>(d_jobs)})
+            REQUIRE(outs[a] != i, "unit_pred_select: an output must not be one of the inputs (which are never written)");
+        for (int b = 0; b < a; ++b) REQUIRE(outs[a] != outs[b], "unit_pred_select: the outputs must be distinct");
+    }
+    return check(launch_unit_pred_select(LS(ctx), bit_depth == 8 ? 1 : 2, d_cand_y, d_cand_c, d_dst_y, dst_stride, d_dst_c, dst_stride_c, d_first, d_best, d_rate, d_jobs, n,
+                                         d_unit_rate, d_unit_cand), "unit_pred_select");
 }
 
 size_t havoc_mi355x_cqt_decide_workspace(int n_ctus) { return cqt_decide_workspace_bytes(n_ctus); }

@@ -1,6 +1,7 @@
 // k_cu_close: closing an inter coding unit -- Search<IfCbf<rqt_root_cbf, transform_tree>>::go (turing/Search.hpp:2362-2568): the CU preamble's bits (cu_skip_flag,
 // pred_mode_flag, part_mode, rqt_root_cbf: turing/SyntaxCtu.hpp:143-264, writers turing/Binarization.h:283-375), the skipped CU, and the comparison of the coded unit
-// with the unit left at its prediction -- and k_unit_pred_ssd: the ssdPrediction that comparison needs (turing/Reconstruct.cpp:856).  DESIGN 7.
+// with the unit left at its prediction -- k_unit_pred_ssd: the ssdPrediction that comparison needs (turing/Reconstruct.cpp:856) -- and k_unit_pred_select: the
+// winning candidate's prediction of every searched unit into the unit prediction planes.  DESIGN 7.
 //
 // k_cu_close's form is k_pu_rate's: a lane per candidate CU, sequential, 64-lane workgroups, the (state, bin) -> (state, rate) table of cabac_tables.h in LDS, the
 // CU's 16 context bytes in two 64-bit registers.  Of the prediction-unit snapshot only merge_idx's byte is ever moved (the skip paths), so it is copied through.
@@ -20,6 +21,7 @@ namespace {
 using CuCloseJob = havoc_mi355x_cu_close_job;
 using CuChoice = havoc_mi355x_cu_choice;
 using PredSsdJob = havoc_mi355x_pred_ssd_job;
+using PredSelectJob = havoc_mi355x_pred_select_job;
 
 static_assert(HAVOC_CU_SYNTAX_CTX_CU_SKIP_FLAG + 2 < 8 && HAVOC_CU_SYNTAX_CTX_PRED_MODE_FLAG < 8 && HAVOC_CU_SYNTAX_CTX_PART_MODE == 7 &&
               HAVOC_CU_SYNTAX_CTX_RQT_ROOT_CBF < 16 && HAVOC_CU_SYNTAX_CTX_BYTES == 16, "the snapshot is walked as two 64-bit words");
@@ -195,7 +197,64 @@ __global__ __launch_bounds__(256) void k_unit_pred_ssd(const char *__restrict__ 
     }
 }
 
+// k_unit_pred_select: the prediction go2 leaves behind for reconstructInter -- the WINNER's (havoc_mi355x_pu_decide's d_best) of a unit's three candidates, copied
+// out of the contiguous candidate blocks into the unit's place in a prediction plane, with the winner's rate and candidate index beside it.  k_unit_pred_ssd's form:
+// a wavefront per unit, wave-uniform on `best`, the 8-byte row pieces of the three planes round the lanes (dword pieces for an 8-bit 4x4 chroma block).  A unit
+// without a winner copies nothing.
+template <int S>
+__global__ __launch_bounds__(256) void k_unit_pred_select(const char *__restrict__ candY, const char *__restrict__ candC, char *__restrict__ dstY, long dstStride,
+                                                          char *__restrict__ dstC, long dstStrideC, const int32_t *__restrict__ first, const int32_t *__restrict__ best,
+                                                          const int64_t *__restrict__ rate, const PredSelectJob *__restrict__ jobs, int n,
+                                                          int64_t *__restrict__ unitRate, int32_t *__restrict__ unitCand)
+{
+    const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= n) return;     // wave-uniform
+    const PredSelectJob job = jobs[i];
+    const int b = best[job.unit];
+    const bool won = b >= 0 && b <= 2;     // wave-uniform; -1: the unit has no winner (a value outside 0..2 selects nothing either)
+    if (lane == 0)
+    {
+        const int cand = won ? first[job.unit] + b : -1;
+        unitCand[job.unit] = cand;
+        unitRate[job.unit] = won ? rate[cand] : -1;
+    }
+    if (!won) return;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+    {
+        const int log2 = job.log2_size - (c > 0), rowBytes = S << log2;
+        const char *a = (c ? candC : candY) + ((long)job.cand_off[c] + ((long)b << 2 * log2)) * S;
+        char *d = (c ? dstC : dstY) + (long)job.dst_off[c] * S;
+        const long sd = (c ? dstStrideC : dstStride) * S;
+        if (rowBytes >= 8)
+        {
+            const int lp = __builtin_ctz(rowBytes) - 3, items = (1 << log2) << lp;     // pieces per row (a power of two), pieces of the block
+            for (int t = lane; t < items; t += 64)
+            {
+                const int y = t >> lp, x = (t & ((1 << lp) - 1)) * 8;
+                st8(d + y * sd + x, ld8(a + (long)y * rowBytes + x));
+            }
+        }
+        else if (lane < 4)      // 4 rows of 4 bytes
+            st4(d + lane * sd, ld4(a + lane * 4));
+    }
+}
+
 } // namespace
+
+hipError_t launch_unit_pred_select(hipStream_t st, int S, const void *candY, const void *candC, void *dstY, long dstStride, void *dstC, long dstStrideC,
+                                   const int32_t *first, const int32_t *best, const int64_t *rate, const PredSelectJob *jobs, int n, int64_t *unitRate, int32_t *unitCand)
+{
+    if (n <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((n + 3) / 4)), block(256);
+    auto c = [](const void *p) { return static_cast<const char *>(p); };
+    auto m = [](void *p) { return static_cast<char *>(p); };
+    if (S == 1)
+        hipLaunchKernelGGL(k_unit_pred_select<1>, grid, block, 0, st, c(candY), c(candC), m(dstY), dstStride, m(dstC), dstStrideC, first, best, rate, jobs, n, unitRate, unitCand);
+    else
+        hipLaunchKernelGGL(k_unit_pred_select<2>, grid, block, 0, st, c(candY), c(candC), m(dstY), dstStride, m(dstC), dstStrideC, first, best, rate, jobs, n, unitRate, unitCand);
+    return hipGetLastError();
+}
 
 hipError_t launch_cu_close(hipStream_t st, const uint8_t *cuSyntax, const uint8_t *puBefore, const uint8_t *puAfter, const int64_t *puRate,
                            const havoc_mi355x_rqt_choice *choice, const havoc_mi355x_rqt_tree_choice *treeChoice, const int64_t *treeRate, const int32_t *predSsd,

@@ -207,7 +207,7 @@ struct RqtTree
     havoc_mi355x_rqt_tree_choice *out;
 };
 
-enum RqtMode { kRqtStandIn, kRqtRated, kRqtTree };
+enum RqtMode { kRqtStandIn, kRqtRated, kRqtTree, kRqtUnits };
 
 __device__ __forceinline__ TuOutcome outcomeOf(const RqtSize &z, int j)
 {
@@ -218,6 +218,10 @@ __device__ __forceinline__ int64_t tuRateOf(const TuOutcome &t) { return (int64_
 // kRqtRated: the residual term is the caller's rate of each candidate (havoc_mi355x_residual_rate: the reference's bits) in place of the stand-in; nothing else differs.
 // kRqtTree: the reference's own comparison -- the rate is the whole transform_tree's of the depth (havoc_mi355x_tree_rate), the distortion ssdY + 4 ssdCb + 4 ssdCr in
 // int32, "coded" means a level in any of the three planes -- and the chroma candidates get their final job records beside the luma ones.
+// kRqtUnits (havoc_mi355x_rqt_decide_units): kRqtTree's decision for units that overlap one another -- the searched units of every size, 64x64 included -- which cannot
+// all be reconstructed into one picture: NO final job record is written (d_final is never touched; recOrigin, recStride, dumpOff and the tree's chroma planes are not
+// read).  A 64x64 unit has depth 1 only (its split is inferred above MaxTbLog2SizeY, Reconstruct.cpp:1300-1310): four 32x32 luma candidates in z.s[3], four Cb and Cr
+// 16x16 candidates in tree.c.s[2]; zeroAt, cb_zero and cr_zero are not read, depth 0 stays untried and depth = 1 exactly when the tree has a level.
 template <int MODE>
 __global__ __launch_bounds__(256) void k_rqt_decide(const RqtUnit *__restrict__ units, int n, const int32_t *__restrict__ zeroAt, const int32_t *__restrict__ oneAt,
                                                     const RqtSizes z, const RqtRates rates, const RqtTree tree, long recOrigin, int recStride, int dumpOff,
@@ -226,16 +230,18 @@ __global__ __launch_bounds__(256) void k_rqt_decide(const RqtUnit *__restrict__ 
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const RqtUnit u = units[i];
-    if (u.log2_size < 3 || u.log2_size > 5)      // a unit has a depth-0 block of 8 .. 32 and four depth-1 blocks of half that: anything else has no size table
+    constexpr bool TREE = MODE == kRqtTree || MODE == kRqtUnits;
+    if (u.log2_size < 3 || u.log2_size > (MODE == kRqtUnits ? 6 : 5))      // a unit has a depth-0 block of 8 .. 32 and four depth-1 blocks of half that: anything else has no size table
     {
         RqtResult bad = RqtResult();
         bad.depth = -1;
         out[i] = bad;
-        if (MODE == kRqtTree) tree.out[i] = havoc_mi355x_rqt_tree_choice();
+        if (TREE) tree.out[i] = havoc_mi355x_rqt_tree_choice();
         return;
     }
-    const RqtSize &s0 = z.s[u.log2_size - 2], &s1 = z.s[u.log2_size - 3];
-    const int j0 = zeroAt[i], j1 = oneAt[i], half = 1 << (u.log2_size - 1);
+    const bool inferred = MODE == kRqtUnits && u.log2_size == 6;      // the split is inferred: the unit has no depth-0 candidate in any plane
+    const RqtSize &s0 = z.s[inferred ? 3 : u.log2_size - 2], &s1 = z.s[u.log2_size - 3];
+    const int j0 = inferred ? 0 : zeroAt[i], j1 = oneAt[i], half = 1 << (u.log2_size - 1);
     // the unit's chroma candidates (kRqtTree): depth 0 one Cb and one Cr block of log2 max(L - 1, 2); depth 1 four of each of log2 L - 2 -- an 8x8 unit's one 4x4
     // block per component is the same candidate at both depths
     const int chromaOne = u.log2_size > 3 ? 4 : 0;
@@ -251,9 +257,9 @@ __global__ __launch_bounds__(256) void k_rqt_decide(const RqtUnit *__restrict__ 
         r.one[k] = outcomeOf(s1, j1 + k);
         ssdOne += (int32_t)r.one[k].ssd;
         coded |= r.one[k].cbf != 0;
-        if (MODE != kRqtTree) rateOne += MODE == kRqtRated ? rates.r[u.log2_size - 3][j1 + k] : tuRateOf(r.one[k]);
+        if (!TREE) rateOne += MODE == kRqtRated ? rates.r[u.log2_size - 3][j1 + k] : tuRateOf(r.one[k]);
     }
-    if (MODE == kRqtTree)
+    if (TREE)
     {
         ca = tree.at[i];
         uint32_t chroma = 0;
@@ -268,13 +274,15 @@ __global__ __launch_bounds__(256) void k_rqt_decide(const RqtUnit *__restrict__ 
         rateOne = tree.rate[2 * i + 1];
     }
     r.cost_one = rateOne + (int64_t)reciprocalLambdaQ16 * (int64_t)ssdOne;
-    if (coded)
+    if (coded && inferred)
+        r.depth = 1;      // the one tree there is (the reference's rqtdepth 0 of a 64x64 unit IS this tree: recorded as what is coded, which is what cu_close reads)
+    else if (coded)
     {
         r.tried_zero = 1;
         r.zero = outcomeOf(s0, j0);
         int32_t ssdZero = (int32_t)r.zero.ssd;
         int64_t rateZero = 0;
-        if (MODE == kRqtTree)
+        if (TREE)
         {
             const uint32_t chroma = c0.d_ssd[ca.cb_zero] + c0.d_ssd[ca.cr_zero];
             tc.chroma_ssd_zero = (int32_t)chroma;
@@ -288,7 +296,8 @@ __global__ __launch_bounds__(256) void k_rqt_decide(const RqtUnit *__restrict__ 
         r.depth = r.cost_zero < r.cost_one ? 0 : 1;      // Reconstruct.cpp:1389
     }
     out[i] = r;
-    if (MODE == kRqtTree) tree.out[i] = tc;
+    if (TREE) tree.out[i] = tc;
+    if (MODE == kRqtUnits) return;
     // every candidate is reconstructed once more: the chosen tree into the picture -- a unit left without residual through its four depth-1 blocks, whose levels are
     // all zero (= the prediction) -- the rest into the dump area
     const bool zeroWins = r.depth == 0 && r.tried_zero;
@@ -385,6 +394,17 @@ hipError_t launch_rqt_decide_tree(hipStream_t st, const RqtUnit *units, int n, c
     const RqtSizes z{{sizes[0], sizes[1], sizes[2], sizes[3]}};
     const RqtTree tree{{{csizes[0], csizes[1], csizes[2], csizes[3]}}, chromaAt, treeRate, treeCbf, cbOrigin, crOrigin, cStride, cDump, treeOut};
     hipLaunchKernelGGL(k_rqt_decide<kRqtTree>, dim3((n + 255) / 256), dim3(256), 0, st, units, n, zeroAt, oneAt, z, RqtRates(), tree, recOrigin, recStride, dumpOff, rlQ16, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_rqt_decide_units(hipStream_t st, const RqtUnit *units, int n, const int32_t *zeroAt, const int32_t *oneAt, const RqtSize sizes[4], const RqtSize csizes[4],
+                                   const havoc_mi355x_rqt_chroma_at *chromaAt, const int64_t *treeRate, const uint32_t *treeCbf, int32_t rlQ16, RqtResult *out,
+                                   havoc_mi355x_rqt_tree_choice *treeOut)
+{
+    if (n <= 0) return hipSuccess;
+    const RqtSizes z{{sizes[0], sizes[1], sizes[2], sizes[3]}};
+    const RqtTree tree{{{csizes[0], csizes[1], csizes[2], csizes[3]}}, chromaAt, treeRate, treeCbf, 0, 0, 0, 0, treeOut};
+    hipLaunchKernelGGL(k_rqt_decide<kRqtUnits>, dim3((n + 255) / 256), dim3(256), 0, st, units, n, zeroAt, oneAt, z, RqtRates(), tree, 0L, 0, 0, rlQ16, out);
     return hipGetLastError();
 }
 

@@ -370,6 +370,8 @@ __global__ __launch_bounds__(64) void k_intra_rate(const int16_t *__restrict__ l
 // second pass; the flag bins are priced after them, in the syntax's order among themselves (cbf_cb and cbf_cr share contexts).  The flag contexts, the luma and the
 // chroma residual contexts are pairwise disjoint, so the sum and every state are those of the interleaved syntax.  A tree without a level is not coded at all
 // (rqt_root_cbf = 0, itself not priced): rate 0, nothing moved.  The alternative form -- luma chain, chroma chain and flags on separate lanes, summed -- was not built.
+// L == 6 exists at depth 1 only: a 64x64 unit lies above MaxTbLog2SizeY, so its split is inferred (Reconstruct.cpp:1300-1310) and the walk is depth 1's without the
+// split_transform_flag bin -- four 32x32 Y and four 16x16 Cb and Cr blocks.  A job of it that claims the bin is coded names an impossible flag value and is refused.
 template <int L, int DEPTH>
 __global__ __launch_bounds__(64) void k_tree_rate(const int16_t *__restrict__ lumaLevels, const int16_t *__restrict__ chromaLevels, const uint8_t *__restrict__ states,
                                                   const uint8_t *__restrict__ syntaxStates, const TreeRateJob *__restrict__ jobs, int njobs, int64_t *__restrict__ rates,
@@ -384,7 +386,8 @@ __global__ __launch_bounds__(64) void k_tree_rate(const int16_t *__restrict__ lu
     TreeRateJob job = TreeRateJob();
     if (j < njobs) job = jobs[j];
     // a job with a flag bit this kernel does not know is not walked: its rate becomes -1, its mask 0 and its snapshots pass through
-    const bool valid = j < njobs && (job.flags & ~HAVOC_TREE_RATE_SPLIT_FLAG_CODED) == 0;
+    // (for L == 6, whose split is inferred, HAVOC_TREE_RATE_SPLIT_FLAG_CODED is such a bit)
+    const bool valid = j < njobs && (job.flags & ~(L <= 5 ? HAVOC_TREE_RATE_SPLIT_FLAG_CODED : 0)) == 0;
     sh.r.ctxIndex[lane] = j < njobs ? job.ctx_index : -1;
     if (j < njobs)
         for (int b = 0; b < HAVOC_INTRA_SYNTAX_CTX_BYTES; ++b) sh.syn[b][lane] = syntaxStates[(long)job.ctx_index * HAVOC_INTRA_SYNTAX_CTX_BYTES + b];
@@ -413,9 +416,9 @@ __global__ __launch_bounds__(64) void k_tree_rate(const int16_t *__restrict__ lu
         if (mask != 0)
         {
             const int cb = (mask & 0x0f0) != 0, cr = (mask & 0xf00) != 0;
-            if (job.flags & HAVOC_TREE_RATE_SPLIT_FLAG_CODED)
+            if (L <= 5 && (job.flags & HAVOC_TREE_RATE_SPLIT_FLAG_CODED))
             {
-                const int ctx = HAVOC_INTRA_SYNTAX_CTX_SPLIT_TRANSFORM_FLAG + 5 - L, e = sh.r.bins[2 * sh.syn[ctx][lane] + DEPTH];
+                const int ctx = HAVOC_INTRA_SYNTAX_CTX_SPLIT_TRANSFORM_FLAG + (L <= 5 ? 5 - L : 0), e = sh.r.bins[2 * sh.syn[ctx][lane] + DEPTH];
                 sh.syn[ctx][lane] = (uint8_t)e;
                 rate += e >> 8;
             }
@@ -462,6 +465,7 @@ hipError_t launch_tree_rate(hipStream_t st, int log2Cb, int depth, const int16_t
     else if (log2Cb == 4 && depth == 1) TREE_RATE(4, 1);
     else if (log2Cb == 5 && depth == 0) TREE_RATE(5, 0);
     else if (log2Cb == 5 && depth == 1) TREE_RATE(5, 1);
+    else if (log2Cb == 6 && depth == 1) TREE_RATE(6, 1);
     else return hipErrorInvalidValue;
 #undef TREE_RATE
     return hipGetLastError();

@@ -56,6 +56,8 @@ hipError_t launch_cu_close(hipStream_t, const uint8_t *, const uint8_t *, const 
                            const int64_t *, const int32_t *, const havoc_mi355x_cu_close_job *, int, int, int32_t, havoc_mi355x_cu_choice *, uint8_t *, uint8_t *);
 hipError_t launch_unit_pred_ssd(hipStream_t, int S, const void *, long, const void *, long, const void *, long, const void *, long, const havoc_mi355x_pred_ssd_job *, int,
                                 int32_t *);
+hipError_t launch_unit_pred_select(hipStream_t, int S, const void *, const void *, void *, long, void *, long, const int32_t *, const int32_t *, const int64_t *,
+                                   const havoc_mi355x_pred_select_job *, int, int64_t *, int32_t *);
 size_t cqt_decide_workspace_bytes(int nctus);
 hipError_t launch_cqt_decide(hipStream_t, int width, int height, int ctbLog2, int minCbLog2, int flags, const uint8_t *, const int32_t *, const havoc_mi355x_cu_choice *, int,
                              void *work, havoc_mi355x_cqt_ctu *, havoc_mi355x_cqt_node *, int8_t *, uint8_t *);
@@ -77,6 +79,9 @@ hipError_t launch_rqt_decide(hipStream_t, const havoc_mi355x_rqt_unit *, int, co
 hipError_t launch_rqt_decide_tree(hipStream_t, const havoc_mi355x_rqt_unit *, int, const int32_t *, const int32_t *, const havoc_mi355x_rqt_size sizes[4],
                                   const havoc_mi355x_rqt_size csizes[4], const havoc_mi355x_rqt_chroma_at *, const int64_t *, const uint32_t *, long, int, int, long, long, int, int,
                                   int32_t, havoc_mi355x_rqt_choice *, havoc_mi355x_rqt_tree_choice *);
+hipError_t launch_rqt_decide_units(hipStream_t, const havoc_mi355x_rqt_unit *, int, const int32_t *, const int32_t *, const havoc_mi355x_rqt_size sizes[4],
+                                   const havoc_mi355x_rqt_size csizes[4], const havoc_mi355x_rqt_chroma_at *, const int64_t *, const uint32_t *, int32_t,
+                                   havoc_mi355x_rqt_choice *, havoc_mi355x_rqt_tree_choice *);
 hipError_t launch_block_cells(hipStream_t, int, int, int, int, const int16_t *, const havoc_mi355x_rqt_unit *, const havoc_mi355x_rqt_choice *, int, havoc_mi355x_cell *, bool);
 hipError_t launch_merge_decide(hipStream_t, const int32_t *, const int32_t *, const int32_t *, int, int64_t, int64_t *, int32_t *);
 hipError_t launch_merge_jobs(hipStream_t, const havoc_mi355x_field_layout *, const int16_t *, const int32_t *, const int32_t *, int, int, havoc_mi355x_pred_bi_job *,

@@ -462,8 +462,15 @@ class DecisionPicture:
     PAD = 96
 
     def __init__(self, hv, width, height, bit_depth=8, qp=32, seed=11, threads=16, frames=None, density=1.0, intra=True, search_on_device=True, distance=1,
-                 sao=False, residual_rates=False, tree_rates=False, pu_modes=False, cu_close=False, cqt=False):
+                 sao=False, residual_rates=False, tree_rates=False, pu_modes=False, cu_close=False, cqt=False, unit_trees=False):
         import torch
+        if unit_trees and not search_on_device:
+            raise ValueError("unit_trees=True needs the device route (search_on_device=True)")
+        if unit_trees and not (tree_rates and pu_modes and cu_close):
+            raise ValueError("unit_trees=True gives every searched unit the tree of its winning prediction and closes it: it needs tree_rates=True, pu_modes=True "
+                             "and cu_close=True")
+        if unit_trees and (width % 8 or height % 8):
+            raise ValueError("unit_trees=True needs a width and a height that are multiples of 8 (the unit prediction planes are addressed in 8-byte pieces)")
         if cqt and not search_on_device:
             raise ValueError("cqt=True needs the device route (search_on_device=True)")
         if cqt and not cu_close:
@@ -497,6 +504,9 @@ class DecisionPicture:
         self.cu_close = cu_close
         # every CTU's coding quadtree decided over those closed units: split_cu_flag's bits and the full / split comparison, CTU after CTU (havoc_mi355x_cqt_decide)
         self.cqt = cqt
+        # the tree, close and quadtree stages run over the SEARCHED units (self.pus), each with the transform tree of its own winning prediction (unit_pred_select,
+        # a second tree plan, rqt_decide_units); the legacy plan over self.units still makes recon / crecon / cells, untouched
+        self.unit_trees = unit_trees
         self.sao = sao                                # in-loop SAO between deblocking and padding (sao_filter_inputs / sao_loop_filter)
         from . import havoc as hmod
         from . import workload
@@ -732,7 +742,7 @@ class DecisionPicture:
         if not ((pus["w"] == pus["h"]) & (pus["part_2Nx2N"] == 1) & (pus["w"] >= 8)).all():
             raise ValueError("pu_modes=True handles 2Nx2N units of 64 to 8 (no merge candidate in go2, bi allowed)")
         M = K * n
-        first, groups, at = np.zeros(n, np.int32), [], 0
+        first, groups, at, cand_y, cand_c = np.zeros(n, np.int32), [], 0, 0, 0
         for log2 in (6, 5, 4, 3):
             sel = np.flatnonzero(pus["w"] == 1 << log2)
             if not len(sel):
@@ -741,6 +751,9 @@ class DecisionPicture:
             first[sel] = at + K * np.arange(len(sel))
             x0, y0 = pus["x0"][sel].astype(np.int64), pus["y0"][sel].astype(np.int64)
             g = dict(log2=log2, nn=nn, sel=sel, m=m, at=at, x0=x0, y0=y0, planes=[])
+            # where the group's prediction blocks lie in the picture's two candidate allocations (samples): luma; Cb, then Cr
+            base = (cand_y, cand_c, cand_c + m * (nn // 2) ** 2)
+            cand_y, cand_c = cand_y + m * nn * nn, cand_c + 2 * m * (nn // 2) ** 2
             for plane in range(3):
                 c = plane > 0
                 size, stride, pad, pe = (nn // 2, self.cstride, self.PAD // 2, self.cpe) if c else (nn, self.stride, self.PAD, self.pe)
@@ -750,10 +763,15 @@ class DecisionPicture:
                 dst = np.arange(m) * size * size
                 sj = np.stack([src * pe + np.repeat(here, K), dst, np.full(m, size), np.full(m, size)], 1).astype(np.int32)
                 g["planes"].append(dict(size=size, stride=stride, taps=4 if c else 8, shift=3 if c else 2, here=here, first_ref=src + 1, pe=pe,
-                                        d_uj=hv.zeros(2 * len(sel) * 8, np.int32), d_bj=hv.zeros(len(sel) * 12, np.int32), d_sj=hv.up(sj),
-                                        d_dst=hv.zeros(m * size * size, self.dt)))
+                                        d_uj=hv.zeros(2 * len(sel) * 8, np.int32), d_bj=hv.zeros(len(sel) * 12, np.int32), d_sj=hv.up(sj), base=base[plane]))
             groups.append(g)
             at += m
+        # every group's blocks in ONE luma and ONE chroma allocation (a job of havoc_mi355x_unit_pred_select names a block by an offset from one base); a group's
+        # buffer is a view of it: groups run from the largest size down, so every block stays aligned to its own size
+        d_cand_y, d_cand_c = hv.zeros(max(cand_y, 1), self.dt), hv.zeros(max(cand_c, 1), self.dt)
+        for g in groups:
+            for plane, q in enumerate(g["planes"]):
+                q["d_dst"] = (d_cand_c if plane else d_cand_y)[q["base"]:q["base"] + g["m"] * q["size"] ** 2]
         jobs = np.zeros(M, hmod.PU_RATE_JOB_DT)
         ctu = ((pus["y0"] // 64) * self.cx + pus["x0"] // 64).astype(np.int32)
         for k in range(K):
@@ -763,7 +781,7 @@ class DecisionPicture:
         jobs["out_index"] = np.arange(M)
         with torch.cuda.stream(hv.tstream):
             i64 = lambda count: torch.zeros(count, dtype=torch.int64, device=hv.device)
-            self.pu_plan = dict(groups=groups, first=first, jobs=jobs, M=M, d_first=hv.up(first), d_count=hv.up(np.full(n, K, np.int32)),
+            self.pu_plan = dict(groups=groups, first=first, jobs=jobs, M=M, d_cand_y=d_cand_y, d_cand_c=d_cand_c, d_first=hv.up(first), d_count=hv.up(np.full(n, K, np.int32)),
                                 d_jobs=torch.zeros(M * hmod.PU_RATE_JOB_DT.itemsize, dtype=torch.uint8, device=hv.device), d_satd=hv.zeros(3 * M, np.int32),
                                 d_rate=i64(M), d_cost=i64(M), d_best=hv.zeros(n, np.int32), d_best_cost=i64(n),
                                 d_after=hv.zeros(M * hmod.PU_SYNTAX_CTX_BYTES, np.uint8), d_best_syntax=hv.zeros(n * hmod.PU_SYNTAX_CTX_BYTES, np.uint8),
@@ -860,13 +878,19 @@ class DecisionPicture:
             return self.cu_plan
         hv, torch, hmod = self.hv, self.torch, self.hmod
         u, pus, P = self.units, self.pus, self._pu_plan()
+        if self.unit_trees:      # the searched units themselves, each charged its WINNER's rate from the winner's snapshot (unit_pred_select, pu_decide), by index
+            u = self._unit_tree_plan()["units"]
         n = len(u)
-        at = {(int(p["x0"]), int(p["y0"]), int(p["w"])): i for i, p in enumerate(pus) if p["part_2Nx2N"] == 1 and p["w"] == p["h"]}
-        match = np.array([at.get((int(x), int(y), 1 << int(l)), -1) for x, y, l in zip(u["x0"], u["y0"], u["log2_size"])], np.int64)
-        cand = np.where(match >= 0, P["first"][np.maximum(match, 0)], 0)          # the unit's L0 candidate
         jobs = np.zeros(n, hmod.CU_CLOSE_JOB_DT)
         jobs["ctx_index"] = jobs["pu_before_index"] = u["ctx_index"]
-        jobs["unit_index"], jobs["pu_rate_index"], jobs["pu_after_index"] = np.arange(n), np.where(match >= 0, cand, -1), cand
+        if self.unit_trees:
+            match = np.arange(n, dtype=np.int64)
+            jobs["unit_index"] = jobs["pu_rate_index"] = jobs["pu_after_index"] = match
+        else:
+            at = {(int(p["x0"]), int(p["y0"]), int(p["w"])): i for i, p in enumerate(pus) if p["part_2Nx2N"] == 1 and p["w"] == p["h"]}
+            match = np.array([at.get((int(x), int(y), 1 << int(l)), -1) for x, y, l in zip(u["x0"], u["y0"], u["log2_size"])], np.int64)
+            cand = np.where(match >= 0, P["first"][np.maximum(match, 0)], 0)          # the unit's L0 candidate
+            jobs["unit_index"], jobs["pu_rate_index"], jobs["pu_after_index"] = np.arange(n), np.where(match >= 0, cand, -1), cand
         jobs["log2_cb_size"], jobs["flags"] = u["log2_size"], np.where(u["log2_size"] == 3, hmod.CU_CLOSE_MIN_CB, 0)
         x, y = u["x0"].astype(np.int64), u["y0"].astype(np.int64)
         hw, hh, c2 = self.W // 2, self.H // 2, self.PAD // 2
@@ -874,6 +898,8 @@ class DecisionPicture:
         here_c = (y // 2 + c2) * self.cstride + x // 2 + c2
         sj["src_off"] = np.stack([(y + self.PAD) * self.stride + x + self.PAD, here_c, 3 * self.cpe + here_c], 1)
         sj["pred_off"] = np.stack([y * self.W + x, (y // 2) * hw + x // 2, hw * hh + (y // 2) * hw + x // 2], 1)
+        if self.unit_trees:      # the unit's block in the unit prediction planes
+            sj["pred_off"] = self.unit_plan["select_jobs"]["dst_off"]
         sj["log2_size"] = u["log2_size"]
         with torch.cuda.stream(hv.tstream):
             up = lambda a: torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).to(hv.device)
@@ -886,6 +912,12 @@ class DecisionPicture:
         """ssdPrediction of every unit in three planes (source against pred / cpred), then the close over what rqt_decide_tree, pu_rate and that launch left on the
         device.  2 launches; asynchronous"""
         hv, Q, P, R = self.hv, self._cu_plan(), self._pu_plan(), self.rqt_plan
+        if self.unit_trees:      # over the searched units: their own prediction planes and trees, the winner's rate and snapshot
+            U = self.unit_plan
+            hv.unit_pred_ssd_d(self.bd, self.d_pic, self.stride, self.d_cpic, self.cstride, U["pred"], self.W, U["cpred"], self.W // 2, Q["d_ssd_jobs"], Q["d_pred_ssd"])
+            hv.cu_close_d(self.d_cu_syntax_states, self.d_pu_syntax_states, P["d_best_syntax"], U["d_unit_rate"], U["d_out"], U["d_tree_out"], U["tree_rate"],
+                          Q["d_pred_ssd"], Q["d_jobs"], P["slice"].max_num_merge_cand, U["rl_q16"], Q["d_out"], Q["d_cu_after"], Q["d_pu_after"])
+            return
         hv.unit_pred_ssd_d(self.bd, self.d_pic, self.stride, self.d_cpic, self.cstride, self.pred, self.W, self.cpred, self.W // 2, Q["d_ssd_jobs"], Q["d_pred_ssd"])
         hv.cu_close_d(self.d_cu_syntax_states, self.d_pu_syntax_states, P["d_after"], P["d_rate"], R["d_out"], R["d_tree_out"], R["tree_rate"], Q["d_pred_ssd"],
                       Q["d_jobs"], P["slice"].max_num_merge_cand, R["rl_q16"], Q["d_out"], Q["d_cu_after"], Q["d_pu_after"])
@@ -894,7 +926,8 @@ class DecisionPicture:
     def cu_decisions(self):
         """what cu_close_launches() left on the device, as numpy, per unit of self.units: dict(records (havoc.CU_CHOICE_DT [n]), cu_syntax [n, 16], pu_syntax [n, 16]
         (the snapshots as the winner left them), pred_ssd int32 [n, 3], jobs (CU_CLOSE_JOB_DT as uploaded), searched [n] (the index in self.pus of the searched unit
-        whose L0 rate was charged, -1: none, the record is refused))"""
+        whose L0 rate was charged, -1: none, the record is refused)).  With unit_trees=True the units are self.pus themselves (searched = arange(n)) and the
+        rate charged is the WINNER's of pu_decide, from the winner's snapshot."""
         if not self.cu_close:
             raise ValueError("cu_decisions: the picture was made without cu_close=True")
         if getattr(self, "_cu_decisions", None) is None:
@@ -916,6 +949,8 @@ class DecisionPicture:
         hv, torch, hmod = self.hv, self.torch, self.hmod
         ctb, mcb = self.CQT_CTB_LOG2, self.CQT_MIN_CB_LOG2
         u, nodes = self.units, hmod.cqt_nodes(ctb, mcb)
+        if self.unit_trees:      # the node table of the searched units: a 64x64 node has a candidate, a node whose four sub-units were searched is compared
+            u = self._unit_tree_plan()["units"]
         x, y, l = u["x0"].astype(np.int64), u["y0"].astype(np.int64), u["log2_size"].astype(np.int64)
         d = ctb - l
         assert (d >= 0).all() and (d <= ctb - mcb).all() and self.cx == -(-self.W >> ctb) and self.cy == -(-self.H >> ctb)
@@ -945,7 +980,8 @@ class DecisionPicture:
         without a candidate and splits, every 32x32 unit stands without a comparison (no node below it has a candidate), a unit whose record cu_close refused refuses
         its CTU (decided = 0), and no full-against-split comparison is live until
         trees exist at every searched size.  What a picture does exercise: the forced splits and deleted quadtrees of a partial last row and column, the depth map,
-        and the context chain over real rows."""
+        and the context chain over real rows.  unit_trees=True lifts the limit: the node table is built from the searched units (self.pus), a 64x64 node has a
+        candidate, a node whose four sub-units were searched is compared, and every CTU is decided."""
         if not self.cqt:
             raise ValueError("cqt_decisions: the picture was made without cqt=True")
         if getattr(self, "_cqt_decisions", None) is None:
@@ -1307,6 +1343,169 @@ class DecisionPicture:
                                 g["ssd2"])
         return P
 
+    # ---- unit_trees=True: the transform tree of EVERY searched unit, made from the residual of its own winning prediction (what reconstructInter runs on after go2) ----
+    def _unit_tree_plan(self):
+        """unit_trees' tables and buffers, built once, beside rqt_plan (which still makes recon / crecon / cells from self.pred).  The units are self.pus in their own
+        order -- 2Nx2N of 64 to 8, overlapping one another as the quadtree search meets them -- so index p means the same unit in pu_decisions, the tree records,
+        cu_decisions and the node table.  Their predictions lie in UNIT PREDICTION PLANES: one luma allocation of four W x H planes and one chroma allocation of four
+        (Cb, Cr) plane pairs, plane 6 - L for units of size 2^L, a unit's block at its picture position (stride W, W / 2 for chroma): a job of any launch names its
+        block by a 32-bit offset, so one base pointer and stride serve a launch that mixes depth-0 blocks of size-L units with depth-1 blocks of size-(L + 1) units.
+        Per transform size the luma candidates (depth 0 of every unit of that size up to 32, then the four depth-1 blocks of every unit of the next larger size, 64
+        included); per chroma size the Cb / Cr candidates as _tree_plan lays them out; a 64x64 unit contributes its four 32x32 luma and four 16x16 Cb and Cr blocks
+        only.  tree_rate jobs per (L, depth): (6, 1) without the flag bit, 5..3 at both depths with it; out_index = 2 * unit + depth.  No final job records."""
+        if hasattr(self, "unit_plan"):
+            return self.unit_plan
+        hv, hmod, torch, bd = self.hv, self.hmod, self.torch, self.bd
+        from . import workload
+        P = self._pu_plan()
+        pus, n = self.pus, len(self.pus)
+        W, hw, hh, c2 = self.W, self.W // 2, self.H // 2, self.PAD // 2
+        if ((pus["x0"].astype(np.int64) + pus["w"] > W) | (pus["y0"].astype(np.int64) + pus["h"] > self.H)).any():
+            raise ValueError("unit_trees=True needs every searched unit inside the picture")
+        u = np.zeros(n, RQT_CU_DT)
+        u["x0"], u["y0"], u["ctx_index"] = pus["x0"], pus["y0"], (pus["y0"] // 64) * self.cx + pus["x0"] // 64
+        for log2 in (6, 5, 4, 3):
+            u["log2_size"][pus["w"] == 1 << log2] = log2
+        ux, uy, uL = u["x0"].astype(np.int64), u["y0"].astype(np.int64), u["log2_size"].astype(np.int64)
+        ypl, cpl = W * self.H, hw * hh                            # a luma plane, a chroma plane
+        uplane = 6 - uL
+        # where the winner's prediction of every unit goes (havoc_mi355x_unit_pred_select) and where cu_close's ssdPrediction reads it
+        sel = np.zeros(n, hmod.PRED_SELECT_JOB_DT)
+        for g in P["groups"]:
+            i = np.arange(len(g["sel"]))
+            sel["cand_off"][g["sel"]] = np.stack([q["base"] + self.PU_CANDIDATES * i * q["size"] ** 2 for q in g["planes"]], 1)
+        sel["dst_off"] = np.stack([uplane * ypl + uy * W + ux, 2 * uplane * cpl + (uy // 2) * hw + ux // 2, (2 * uplane + 1) * cpl + (uy // 2) * hw + ux // 2], 1)
+        sel["log2_size"], sel["unit"] = uL, np.arange(n)
+        lists, clists = {s: [] for s in (2, 3, 4, 5)}, {s: [] for s in (2, 3, 4)}
+        zero_at, one_at, chroma_at = np.full(n, -1, np.int32), np.zeros(n, np.int32), np.zeros(n, hmod.RQT_CHROMA_AT_DT)
+        for i in range(n):
+            L, a = int(uL[i]), chroma_at[i]
+            if L < 6:
+                zero_at[i] = len(lists[L])
+                lists[L].append((i, 0, 0))
+                c0 = max(L - 1, 2)
+                a["cb_zero"], a["cr_zero"] = len(clists[c0]), len(clists[c0]) + 1
+                clists[c0] += [(i, 0, 1, 0), (i, 0, 2, 0)]
+            else:       # a 64x64 unit has no depth-0 candidate in any plane (its split is inferred)
+                a["cb_zero"], a["cr_zero"] = -1, -1
+            one_at[i] = len(lists[L - 1])
+            lists[L - 1] += [(i, 1, k) for k in range(4)]
+            if L > 3:
+                a["cb_one"], a["cr_one"] = len(clists[L - 2]), len(clists[L - 2]) + 4
+                clists[L - 2] += [(i, 1, comp, k) for comp in (1, 2) for k in range(4)]
+            else:
+                a["cb_one"], a["cr_one"] = a["cb_zero"], a["cr_zero"]
+        plan = dict(units=u, select_jobs=sel, zero_at=zero_at, one_at=one_at, chroma_at=chroma_at, sizes={}, csizes={}, tree_jobs={}, table=np.zeros((4, 5), np.uint64),
+                    ctable=np.zeros((4, 5), np.uint64), rl_q16=int((1.0 / self.lam) * 65536 + 0.5), launches=2,
+                    pred=hv.zeros(4 * ypl, self.dt), cpred=hv.zeros(8 * cpl, self.dt), d_units=hv.up(np.ascontiguousarray(u).view(np.int32)), d_zero_at=hv.up(zero_at),
+                    d_one_at=hv.up(one_at), d_chroma_at=hv.up(np.ascontiguousarray(chroma_at).view(np.int32)), d_out=hv.zeros(n * 26, np.int32),
+                    d_tree_out=hv.zeros(4 * n, np.int32), tree_cbf=hv.zeros(2 * n, np.int32), d_unit_cand=hv.zeros(n, np.int32))
+
+        def group(log2, jobs, ctx, c_idx):
+            m, area = len(jobs), 1 << 2 * log2
+            qs, qshift, _ = workload.quant_params(self.qp, log2, bd, False)
+            inv, dshift = workload.dequant_params(self.qp, log2, bd)
+            if c_idx is None:
+                qs, qshift, inv, dshift = (int(v) for v in self.quant[log2 - 2])
+            rj = np.zeros(m, hmod.RDOQ_JOB_DT)
+            rj["dst_off"] = rj["src_off"] = jobs[:, 0]
+            rj["quant_scale"], rj["quant_shift"], rj["inv_scale"] = qs, qshift, inv
+            rj["lambda_q16"], rj["sdh_factor"] = hmod.rdoq_lambda(self.lam, inv)
+            rj["sdh"], rj["ctx_index"] = 1, ctx
+            if c_idx is not None:
+                rj["c_idx"] = c_idx
+            with torch.cuda.stream(hv.tstream):
+                d_rj = torch.from_numpy(rj.view(np.uint8).reshape(-1)).to(hv.device)
+            return dict(log2=log2, nn=1 << log2, m=m, inv=inv, dshift=dshift, jobs=jobs, d_jobs=hv.up(jobs), d_rj=d_rj, coef=hv.zeros(m * area, np.int16),
+                        level=hv.zeros(m * area, np.int16), piece=hv.zeros(m * area, self.dt), work=hv.rdoq_workspace(m), cbf=hv.zeros(m, np.int32),
+                        ssd=hv.zeros(m, np.uint32))
+
+        for log2, cand in lists.items():
+            if not cand:
+                continue
+            nn, c = 1 << log2, np.array(cand, np.int64)
+            x = ux[c[:, 0]] + np.where(c[:, 1] == 1, (c[:, 2] & 1) * nn, 0)
+            y = uy[c[:, 0]] + np.where(c[:, 1] == 1, (c[:, 2] >> 1) * nn, 0)
+            at = np.arange(len(c)) << 2 * log2
+            jobs = np.stack([at, self.origin + y * self.stride + x, uplane[c[:, 0]] * ypl + y * W + x, at], 1).astype(np.int32)
+            g = plan["sizes"][log2] = group(log2, jobs, u["ctx_index"][c[:, 0]], None)
+            plan["table"][log2 - 2] = [g["cbf"].data_ptr(), g["ssd"].data_ptr(), 0, g["d_jobs"].data_ptr(), 0]
+            plan["launches"] += 3
+        for cl, cand in clists.items():
+            if not cand:
+                continue
+            cn, c = 1 << cl, np.array(cand, np.int64)
+            x = ux[c[:, 0]] // 2 + np.where(c[:, 1] == 1, (c[:, 3] & 1) * cn, 0)
+            y = uy[c[:, 0]] // 2 + np.where(c[:, 1] == 1, (c[:, 3] >> 1) * cn, 0)
+            comp, at = c[:, 2], np.arange(len(c)) << 2 * cl
+            jobs = np.stack([at, 3 * (comp - 1) * self.cpe + (y + c2) * self.cstride + x + c2, (2 * uplane[c[:, 0]] + comp - 1) * cpl + y * hw + x, at], 1).astype(np.int32)
+            g = plan["csizes"][cl] = group(cl, jobs, u["ctx_index"][c[:, 0]], comp)
+            g["cand"] = c
+            plan["ctable"][cl - 2] = [g["cbf"].data_ptr(), g["ssd"].data_ptr(), 0, g["d_jobs"].data_ptr(), 0]
+            plan["launches"] += 3
+        for L in (6, 5, 4, 3):
+            at = np.flatnonzero(uL == L)
+            if not len(at):
+                continue
+            c0, c1 = max(L - 1, 2), max(L - 2, 2)
+            for depth in ((1,) if L == 6 else (0, 1)):
+                tj = np.zeros(len(at), hmod.TREE_RATE_JOB_DT)
+                if depth == 0:
+                    tj["luma_off"], tj["cb_off"], tj["cr_off"] = zero_at[at] << 2 * L, chroma_at["cb_zero"][at] << 2 * c0, chroma_at["cr_zero"][at] << 2 * c0
+                else:
+                    tj["luma_off"], tj["cb_off"], tj["cr_off"] = one_at[at] << 2 * (L - 1), chroma_at["cb_one"][at] << 2 * c1, chroma_at["cr_one"][at] << 2 * c1
+                tj["ctx_index"], tj["out_index"], tj["sdh"] = u["ctx_index"][at], 2 * at + depth, 1
+                tj["flags"] = hmod.TREE_RATE_SPLIT_FLAG_CODED if L < 6 else 0      # above MaxTbLog2SizeY the split is inferred: no bin
+                with torch.cuda.stream(hv.tstream):
+                    d_tj = torch.from_numpy(tj.view(np.uint8).reshape(-1).copy()).to(hv.device)
+                plan["tree_jobs"][L, depth] = dict(jobs=tj, d_jobs=d_tj, luma=L - depth, chroma=c1 if depth else c0)
+                plan["launches"] += 1
+        with torch.cuda.stream(hv.tstream):
+            plan["tree_rate"] = torch.zeros(2 * n, dtype=torch.int64, device=hv.device)
+            plan["d_unit_rate"] = torch.zeros(n, dtype=torch.int64, device=hv.device)
+            plan["d_select_jobs"] = torch.from_numpy(sel.view(np.uint8).reshape(-1).copy()).to(hv.device)
+        self.unit_plan = plan
+        return plan
+
+    def unit_tree_launches(self):
+        """behind pu_mode_launches: the winner's prediction of every searched unit into the unit prediction planes with its rate (one launch for every size), then per
+        transform size the luma candidates and per chroma size the Cb / Cr candidates (residual + DCT -> RDOQ from the CTU's snapshot -> IQ + IDCT + add -> SSD, into
+        pieces), the whole-tree rate and cbf mask per (unit size, depth), and the decision over three planes without final records.  Asynchronous"""
+        hv, bd, P, U = self.hv, self.bd, self._pu_plan(), self._unit_tree_plan()
+        hw = self.W // 2
+        hv.unit_pred_select_d(bd, P["d_cand_y"], P["d_cand_c"], U["pred"], self.W, U["cpred"], hw, P["d_first"], P["d_best"], P["d_rate"], U["d_select_jobs"],
+                              U["d_unit_rate"], U["d_unit_cand"])
+        for groups, src, stride, pred, pstride in ((U["sizes"], self.d_pic, self.stride, U["pred"], self.W), (U["csizes"], self.d_cpic, self.cstride, U["cpred"], hw)):
+            for g in groups.values():
+                hv.tu_forward_d(bd, 0, g["log2"], g["coef"], src, stride, pred, pstride, g["d_jobs"].view(-1, 4))
+                hv.rdoq_d(bd, g["log2"], g["level"], g["coef"], self.d_states, g["d_rj"], g["cbf"], g["work"])
+                hv.tu_reconstruct_d(bd, 0, g["log2"], g["inv"], g["dshift"], g["piece"], g["nn"], pred, pstride, src, stride, g["level"], g["d_jobs"].view(-1, 4), g["ssd"])
+        for (L, depth), t in U["tree_jobs"].items():
+            hv.tree_rate_d(L, depth, U["sizes"][t["luma"]]["level"], U["csizes"][t["chroma"]]["level"], self.d_states, self.d_syntax_states, t["d_jobs"], U["tree_rate"],
+                           U["tree_cbf"])
+        hv.rqt_decide_units_d(U["d_units"].view(-1, 4), U["d_zero_at"], U["d_one_at"], U["table"], U["ctable"], U["d_chroma_at"], U["tree_rate"], U["tree_cbf"],
+                              U["rl_q16"], U["d_out"], U["d_tree_out"])
+
+    def unit_tree_decisions(self, planes=False):
+        """what unit_tree_launches() left on the device, as numpy, per unit of self.pus: dict(units (RQT_CU_DT), choice (RQT_RESULT_DT: rqt_decide_units' records -- a
+        64x64 unit has depth 1 when its one tree is coded, else 0, depth 0 untried), tree_choice (havoc.RQT_TREE_RESULT_DT), tree_rate int64 [n, 2] and tree_cbf uint32
+        [n, 2] (per depth; entry 0 of a 64x64 unit is nobody's), unit_rate int64 [n] and unit_cand int32 [n] (the winner's PU rate and candidate index, -1 without a
+        winner)); planes=True adds pred (dt [4, H, W]: plane 6 - L holds the units of size 2^L) and cpred (dt [4, 2, H / 2, W / 2])"""
+        if not self.unit_trees:
+            raise ValueError("unit_tree_decisions: the picture was made without unit_trees=True")
+        hv, U, hmod = self.hv, self._unit_tree_plan(), self.hmod
+        if getattr(self, "_unit_tree_decisions", None) is None:
+            with self.torch.cuda.stream(hv.tstream):
+                rate, unit_rate = U["tree_rate"].cpu().numpy().reshape(-1, 2), U["d_unit_rate"].cpu().numpy()
+            self._unit_tree_decisions = dict(units=U["units"], choice=hv.down(U["d_out"], np.int32).view(RQT_RESULT_DT).copy(),
+                                             tree_choice=hv.down(U["d_tree_out"], np.int32).view(hmod.RQT_TREE_RESULT_DT).copy(), tree_rate=rate,
+                                             tree_cbf=hv.down(U["tree_cbf"], np.int32).view(np.uint32).reshape(-1, 2), unit_rate=unit_rate,
+                                             unit_cand=hv.down(U["d_unit_cand"], np.int32))
+        if not planes:
+            return self._unit_tree_decisions
+        return dict(self._unit_tree_decisions, pred=hv.down(U["pred"], self.dt).reshape(4, self.H, self.W),
+                    cpred=hv.down(U["cpred"], self.dt).reshape(4, 2, self.H // 2, self.W // 2))
+
     @property
     def rqt_tree_results(self):
         """tree_rates=True: what the decision over three planes adds per unit (havoc.RQT_TREE_RESULT_DT: both cbf masks, both sums ssdCb + ssdCr): downloaded when
@@ -1459,7 +1658,9 @@ class DecisionPicture:
             # everything after the searches is a FIXED sequence of launches over device-resident tables (the decided field never leaves the device, the decisions
             # between the launches are kernels): recorded once into a HIP graph, one launch per picture, one wait at the end
             self._rqt = self._cells = self._sao_decisions = self._rqt_rates = self._rqt_tree = self._cu_decisions = self._cqt_decisions = None
+            self._unit_tree_decisions = None
             pu = (self.pu_mode_launches,) if self.pu_modes else ()      # (the tables its launches read went up before the replay: pu_candidates)
+            pu += (self.unit_tree_launches,) if self.unit_trees else ()  # (behind pu_decide: it reads the winners in place; before cu_close, which reads its records)
             pu += (self.cu_close_launches,) if self.cu_close else ()     # (after the tree decisions AND the prediction units' rates: it reads both in place)
             pu += (self.cqt_launch,) if self.cqt else ()                 # (behind cu_close: it reads its records in place)
             if self.sao:
@@ -1535,6 +1736,8 @@ class DecisionPicture:
             raise ValueError("step_banded does not close coding units: use step() with cu_close=True")
         if self.cqt:
             raise ValueError("step_banded does not decide coding quadtrees: use step() with cqt=True")
+        if self.unit_trees:
+            raise ValueError("step_banded does not build the searched units' trees: use step() with unit_trees=True")
         if self.sao:
             # SAO of band b reads the deblocked rows of band b + 1 (turing/TaskSao.cpp:46-56): not built
             raise ValueError("step_banded does not run SAO: use step() with sao=True")
@@ -1616,7 +1819,8 @@ class DecisionPicture:
 
     def results(self):
         """what the TU chain left on the device, as numpy (per group): coefficients, levels, flags, SSDs; and the reconstruction; with pu_modes=True a third entry,
-        dict(pu_modes=self.pu_decisions), with cu_close=True also cu_close=self.cu_decisions, with cqt=True also cqt=self.cqt_decisions"""
+        dict(pu_modes=self.pu_decisions), with cu_close=True also cu_close=self.cu_decisions, with cqt=True also cqt=self.cqt_decisions, with unit_trees=True also
+        unit_trees=self.unit_tree_decisions()"""
         hv = self.hv
         out = [dict(log2=g["log2"], coef=hv.down(g["coef"], np.int16), level=hv.down(g["level"], np.int16), cbf=hv.down(g["cbf"], np.int32),
                     ssd=hv.down(g["ssd"], np.uint32)) for g in self.groups]
@@ -1626,5 +1830,7 @@ class DecisionPicture:
                 extra["cu_close"] = self.cu_decisions
             if self.cqt:
                 extra["cqt"] = self.cqt_decisions
+            if self.unit_trees:
+                extra["unit_trees"] = self.unit_tree_decisions()
             return out, hv.down(self.recon, self.dt), extra
         return out, hv.down(self.recon, self.dt)

@@ -135,10 +135,12 @@ def _load():
         "pu_decide": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp],
         "cu_close": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_int32, _vp, _vp, _vp],
         "unit_pred_ssd": [_vp, _i, _vp, C.c_ssize_t, _vp, C.c_ssize_t, _vp, C.c_ssize_t, _vp, C.c_ssize_t, _vp, _i, _vp],
+        "unit_pred_select": [_vp, _i, _vp, _vp, _vp, C.c_ssize_t, _vp, C.c_ssize_t, _vp, _vp, _vp, _vp, _i, _vp, _vp],
         "cqt_decide": [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, C.c_size_t, _vp, _vp, _vp, _vp],
         "intra_decide_rated": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_int32, _vp, _vp],
         "rqt_decide_rated": [_vp, _vp, _i, _vp, _vp, _vp, _vp, C.c_int64, C.c_ssize_t, _i, _i, _vp],
         "rqt_decide_tree": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_ssize_t, _i, C.c_int64, C.c_int64, C.c_ssize_t, _i, _i, _vp, _vp],
+        "rqt_decide_units": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp],
         "sao_stats": [_vp, _i, _i, _vp, _ip, _vp, _ip, _vp, _i, _vp],
         "sao_filter": [_vp, _i, _i, _vp, _ip, _vp, _ip, _vp, _i],
         "sao_band_chroma": [_vp, _i, _i, _vp, _ip, _vp, _ip, _vp, _i, _vp],
@@ -345,6 +347,9 @@ CU_CHOICE_DT = np.dtype([("outcome", "<i4"), ("have_residual", "<i4"), ("rate", 
                          ("cost_no_residual", "<i8")])
 PRED_SSD_JOB_DT = np.dtype([("src_off", "<i4", 3), ("pred_off", "<i4", 3), ("log2_size", "<i4"), ("reserved", "<i4")])
 assert CU_CLOSE_JOB_DT.itemsize == 32 and CU_CHOICE_DT.itemsize == 48 and PRED_SSD_JOB_DT.itemsize == 32
+# one havoc_mi355x_pred_select_job, 32 bytes: where a unit's three candidate predictions lie and where the winner's goes (offsets in samples per plane: Y, Cb, Cr)
+PRED_SELECT_JOB_DT = np.dtype([("cand_off", "<i4", 3), ("dst_off", "<i4", 3), ("log2_size", "<i4"), ("unit", "<i4")])
+assert PRED_SELECT_JOB_DT.itemsize == 32
 CU_CLOSE_MIN_CB, CU_CLOSE_AMP, CU_CLOSE_MERGE_2Nx2N = 1, 2, 4
 CU_OUTCOME_REFUSED, CU_OUTCOME_CODED, CU_OUTCOME_NO_RESIDUAL, CU_OUTCOME_SKIPPED = -1, 0, 1, 2
 CU_SYNTAX_CTX_BYTES = 16        # HAVOC_CU_SYNTAX_CTX_*: split_cu_flag[3], cu_skip_flag[3], pred_mode_flag, part_mode[4], rqt_root_cbf, 4 reserved
@@ -608,6 +613,13 @@ class Havoc:
         self._ck(self.L.havoc_mi355x_rqt_decide_tree(self.h, _ptr(units), units.shape[0], _ptr(zero_at), _ptr(one_at), sizes.ctypes.data, csizes.ctypes.data, _ptr(chroma_at),
                                                      _ptr(tree_rates), _ptr(tree_cbf), int(rec_origin), int(rec_stride), int(dump_off), int(cb_origin), int(cr_origin),
                                                      int(c_stride), int(c_dump_off), int(rl_q16), _ptr(out), _ptr(tree_out)))
+
+    def rqt_decide_units_d(self, units, zero_at, one_at, sizes, csizes, chroma_at, tree_rates, tree_cbf, rl_q16, out, tree_out):
+        """rqt_decide_tree_d for units that overlap one another (havoc_mi355x_rqt_decide_units): the same records, no final job records -- the d_stats, d_jobs and
+        d_final columns of `sizes` / `csizes` may be 0 -- and units of log2_size 6, which have depth 1 only (four 32x32 luma candidates in sizes[3], four Cb and Cr
+        16x16 in csizes[2]; rate and mask at entry 2 i + 1)"""
+        self._ck(self.L.havoc_mi355x_rqt_decide_units(self.h, _ptr(units), units.shape[0], _ptr(zero_at), _ptr(one_at), sizes.ctypes.data, csizes.ctypes.data, _ptr(chroma_at),
+                                                      _ptr(tree_rates), _ptr(tree_cbf), int(rl_q16), _ptr(out), _ptr(tree_out)))
 
     def block_cells_add_d(self, width, height, qp, dpb_index0, field, units, decisions, cells):
         """the cells of `units` into cells that keep what they hold elsewhere (havoc_mi355x_block_cells_add)"""
@@ -981,7 +993,8 @@ class Havoc:
     def tree_rate_d(self, log2_cb, depth, luma_levels, chroma_levels, states, syntax_states, jobs, rates, cbf, states_out=None, syntax_states_out=None):
         """the CABAC rate of an inter unit's whole transform tree at one depth: split_transform_flag, cbf_cb, cbf_cr, cbf_luma and the Y, Cb, Cr residual_coding
         (havoc_mi355x_tree_rate); jobs: uint8 tensor holding TREE_RATE_JOB_DT records; rates: int64 tensor; cbf: int32 tensor (the masks); the two outputs: None, or
-        128 / 4 bytes per job.  No sync."""
+        128 / 4 bytes per job.  log2_cb 3..5 at depth 0 or 1; 6 at depth 1 only (a 64x64 unit's one tree, its split inferred: no flag bin, and a job that claims
+        one is refused with rate -1).  No sync."""
         self._ck(self.L.havoc_mi355x_tree_rate(self.h, log2_cb, depth, _ptr(luma_levels), _ptr(chroma_levels), _ptr(states), _ptr(syntax_states), _ptr(jobs),
                                                jobs.numel() // TREE_RATE_JOB_DT.itemsize, _ptr(rates), _ptr(cbf), _ptr(states_out), _ptr(syntax_states_out)))
 
@@ -1129,6 +1142,31 @@ class Havoc:
         self._ck(self.L.havoc_mi355x_unit_pred_ssd(self.h, bit_depth, _ptr(planes[0]), src_stride, _ptr(planes[1]), src_stride_c, _ptr(planes[2]), pred_stride,
                                                    _ptr(planes[3]), pred_stride_c, _ptr(j), n, _ptr(out)))
         return self.down(out, np.int32)[:3 * n].reshape(-1, 3)
+
+    def unit_pred_select_d(self, bit_depth, cand_y, cand_c, dst_y, dst_stride, dst_c, dst_stride_c, first, best, rate, jobs, unit_rate, unit_cand):
+        """the winning candidate's Y, Cb and Cr block of every unit out of the candidate buffers into prediction planes, and the winner's rate and candidate index
+        (havoc_mi355x_unit_pred_select); first / best: int32 tensors and rate: int64 tensor as pu_decide_d / pu_rate_d leave them; jobs: uint8 tensor of
+        PRED_SELECT_JOB_DT; unit_rate: int64, unit_cand: int32, per unit.  No sync."""
+        self._ck(self.L.havoc_mi355x_unit_pred_select(self.h, bit_depth, _ptr(cand_y), _ptr(cand_c), _ptr(dst_y), dst_stride, _ptr(dst_c), dst_stride_c, _ptr(first),
+                                                      _ptr(best), _ptr(rate), _ptr(jobs), jobs.numel() // PRED_SELECT_JOB_DT.itemsize, _ptr(unit_rate), _ptr(unit_cand)))
+
+    def unit_pred_select(self, bit_depth, cand_y, cand_c, dst_y, dst_stride, dst_c, dst_stride_c, first, best, rate, jobs):
+        """numpy level: the candidate buffers and the destination planes as they are before (uint8, or uint16 above 8 bits), first / best int32 and rate int64 per
+        unit / candidate, PRED_SELECT_JOB_DT jobs -> (the luma planes after, the chroma planes after, unit_rate int64, unit_cand int32 [len(best)], the entries no
+        job names 0)"""
+        t, dt = self.torch, np.uint8 if bit_depth == 8 else np.uint16
+        jobs = np.ascontiguousarray(jobs, PRED_SELECT_JOB_DT)
+        n, nu = len(jobs), len(best)
+        with t.cuda.stream(self.tstream):
+            up = lambda a, d: t.from_numpy(np.ascontiguousarray(a, d).reshape(-1).view(np.uint8).copy()).to(self.device)
+            planes = [up(a, dt) for a in (cand_y, cand_c, dst_y, dst_c)]
+            d_first, d_best, d_rate = up(first, np.int32), up(best, np.int32), up(rate, np.int64)
+            j = up(jobs.view(np.uint8), np.uint8) if n else t.zeros(32, dtype=t.uint8, device=self.device)
+            unit_rate, unit_cand = t.zeros(max(nu, 1), dtype=t.int64, device=self.device), t.zeros(max(nu, 1), dtype=t.int32, device=self.device)
+        self._ck(self.L.havoc_mi355x_unit_pred_select(self.h, bit_depth, _ptr(planes[0]), _ptr(planes[1]), _ptr(planes[2]), dst_stride, _ptr(planes[3]), dst_stride_c,
+                                                      _ptr(d_first), _ptr(d_best), _ptr(d_rate), _ptr(j), n, _ptr(unit_rate), _ptr(unit_cand)))
+        return (self.down(planes[2], np.uint8).view(dt).copy(), self.down(planes[3], np.uint8).view(dt).copy(), self.down(unit_rate, np.int64)[:nu],
+                self.down(unit_cand, np.int32)[:nu])
 
     def intra_rate_jobs_d(self, mpm, order, count, slot, rdoq_jobs, n, flags, jobs):
         """INTRA_RATE_JOB_DT records of the candidates intra_expand laid out (havoc_mi355x_intra_rate_jobs): job c = candidate slot c; jobs: uint8 tensor.  No sync."""

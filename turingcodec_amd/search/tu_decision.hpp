@@ -77,6 +77,12 @@ havoc_rqt_result decideRqt(View &view, const havoc_rqt_cu &cu, Lambda reciprocal
         r.tried_zero = 0;
         return r;
     }
+    if (cu.log2_size > 5)            // a 64x64 unit lies above MaxTbLog2SizeY: the split is inferred (Reconstruct.cpp:1300-1310) and the four-block tree is the only one
+    {                                // there is -- the reference's rqtdepth 0 of such a unit; recorded as depth 1, the tree that is coded, depth 0 untried
+        r.depth = 1;
+        r.tried_zero = 0;
+        return r;
+    }
     r.tried_zero = 1;
     r.zero = view.evaluate(cu.x0, cu.y0, cu.log2_size, 0);
     const ChromaOutcome c0 = chroma(0);
