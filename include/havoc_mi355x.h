@@ -1162,6 +1162,78 @@ int havoc_mi355x_cqt_decide(havoc_mi355x_ctx *ctx, int width, int height, int ct
                             const int32_t *d_node_cu, const havoc_mi355x_cu_choice *d_choice, int n_choice, void *d_work, size_t work_bytes,
                             havoc_mi355x_cqt_ctu *d_ctu, havoc_mi355x_cqt_node *d_node, int8_t *d_depth, uint8_t *d_cu_syntax_out);
 
+/* ---- acting on the decided quadtree: the final coding units into ONE picture and a per-cell field (csrc/kernels_cqt.hip: k_cqt_commit) ----
+ * What the reference's picture holds once Search<coding_quadtree>::go has kept a CTU's winner (turing/Search.hpp:808-886 over :2362-2568): of the searched units --
+ * which overlap one another, one per node of every CTU's quadtree -- exactly the FINAL coding units of the decided trees, each as havoc_mi355x_cu_close closed it.
+ * Nothing is computed: every sample was made by the calls before (havoc_mi355x_unit_pred_select: the winner's prediction; havoc_mi355x_tu_reconstruct: the
+ * candidate pieces of both transform depths); this call selects.  One launch over the n searched units, whatever was decided: a fixed size, capturable.
+ * Unit p (d_units[p]; index p means the same unit in every table) is committed exactly when
+ *   - its CTU c (raster index of (x0 >> ctb_log2, y0 >> ctb_log2)) has d_ctu[c].decided == 1;
+ *   - its node k = (4^d - 1) / 3 + z, d = ctb_log2 - log2_size, z the z-order index of its place in the CTU, has d_node_cu[c N + k] == p;
+ *   - d_node[c N + k] has HAVOC_CQT_NODE_FINAL and choice == HAVOC_CQT_CU;
+ *   - d_cu[p].outcome is HAVOC_CU_OUTCOME_CODED, _NO_RESIDUAL or _SKIPPED.
+ * Every other unit writes nothing.  A unit whose origin or size has no node in the table -- log2_size outside min_cb_log2..ctb_log2, an origin that is negative or not
+ * a multiple of its size, a block that leaves the picture -- is skipped, not followed.  The final units of a CTU partition it: no two units write the same sample or cell.
+ * What is written, by outcome:
+ *   - NO_RESIDUAL, SKIPPED: the unit's block of the prediction planes, three planes: (1 << log2_size)^2 samples at d_pred_y + d_pred_off[3 p] (rows pred_stride
+ *     apart), half that size at d_pred_c + d_pred_off[3 p + 1] (Cb) and [3 p + 2] (Cr) (rows pred_stride_c apart): havoc_mi355x_pred_select_job's dst_off;
+ *   - CODED: the candidate pieces of the depth that stands, t = (log2_size < 6 && d_choice[p].depth == 0 && d_choice[p].tried_zero) ? 0 : 1 (havoc_mi355x_cu_close's
+ *     rule; a 64x64 unit has depth-1 pieces only).  Candidate j of transform size s is the contiguous (1 << s)^2 block at  j << 2 s  samples of luma_pieces[s - 2]
+ *     (s = 2..5) or chroma_pieces[s - 2] (s = 2..4), where the unit plan's havoc_mi355x_tu_reconstruct launches leave it.  Luma: t == 0 the piece d_zero_at[p] of size
+ *     log2_size, t == 1 the four pieces d_one_at[p] .. + 3 of size log2_size - 1 in z-order.  Cb / Cr: t == 0, or an 8x8 unit (whose one 4x4 block per component
+ *     serves both depths), the piece cb_zero / cr_zero of size log2_size - 1; else the four pieces cb_one / cr_one .. + 3 of size log2_size - 2.  A block of the
+ *     tree with cbf 0 needs no case of its own: its piece is the clipped prediction.  A piece pointer no committed unit needs may be NULL.
+ * Destination: luma at d_rec_y + rec_origin + y * rec_stride + x, Cb / Cr at d_rec_c + cb_origin / cr_origin + (y / 2) * c_stride + x / 2; offsets and strides in
+ * samples of 1 (bit_depth 8) or 2 bytes; no alignment is asked of them (rows move in unaligned 8-byte pieces, 4-byte pieces for an 8-bit 4x4 block).
+ * d_cells: one record per MinCb cell, (height >> min_cb_log2) rows of (width >> min_cb_log2).  The call first sets the WHOLE map to all-ones bytes (an asynchronous
+ * fill), then the wavefront that commits a unit writes the unit's cells.  The samples of an undecided CTU are left as they were and its cells stay all-ones (unit -1);
+ * when every `decided` is 0 -- a wait of havoc_mi355x_cqt_decide gave up -- nothing but the fill happens.
+ * d_cand_mv: int16 [candidates][2 lists][x, y] in quarter samples, indexed by d_unit_cand[p]; may be NULL: the cells then carry zero vectors.  d_best[p]: 0 L0, 1 L1,
+ * 2 bi (havoc_mi355x_pu_decide's). */
+typedef struct {
+    int32_t unit;        /* index of the coding unit that covers the cell; -1: none (its CTU is undecided) */
+    int32_t cand;        /* d_unit_cand[unit]: the winning candidate */
+    int16_t mv[2][2];    /* [list][x, y]; a list the mode does not use: 0, 0 */
+    uint8_t log2_size;   /* of the coding unit */
+    uint8_t outcome;     /* HAVOC_CU_OUTCOME_CODED / NO_RESIDUAL / SKIPPED */
+    uint8_t pred;        /* 0 L0, 1 L1, 2 bi */
+    uint8_t tr_depth;    /* 0 / 1 of the tree that stands; 0 when nothing is coded */
+    uint32_t cbf;        /* the standing tree's mask as havoc_mi355x_rqt_tree_choice records it; 0 unless CODED */
+} havoc_mi355x_cqt_cell;   /* sizeof: 24 */
+typedef struct {
+    int32_t bit_depth;                  /* 8..16 */
+    int32_t width, height, ctb_log2, min_cb_log2;       /* havoc_mi355x_cqt_decide's rules */
+    int32_t n;                          /* searched units */
+    const havoc_mi355x_rqt_unit *d_units;
+    const int32_t *d_node_cu;           /* as havoc_mi355x_cqt_decide read it */
+    const havoc_mi355x_cqt_ctu *d_ctu;  /* ... and wrote them */
+    const havoc_mi355x_cqt_node *d_node;
+    const havoc_mi355x_cu_choice *d_cu;
+    const havoc_mi355x_rqt_choice *d_choice;
+    const havoc_mi355x_rqt_tree_choice *d_tree_choice;
+    const int32_t *d_zero_at, *d_one_at;
+    const havoc_mi355x_rqt_chroma_at *d_chroma_at;
+    const void *luma_pieces[4];         /* transform sizes 2..5 */
+    const void *chroma_pieces[3];       /* 2..4 */
+    const void *d_pred_y, *d_pred_c;
+    intptr_t pred_stride, pred_stride_c;
+    const int32_t *d_pred_off;          /* [n][3] */
+    const int32_t *d_best, *d_unit_cand;
+    const int16_t *d_cand_mv;           /* or NULL */
+    void *d_rec_y;
+    int64_t rec_origin;
+    intptr_t rec_stride;
+    void *d_rec_c;
+    int64_t cb_origin, cr_origin;
+    intptr_t c_stride;
+    havoc_mi355x_cqt_cell *d_cells;
+} havoc_mi355x_cqt_commit_args;         /* sizeof: 288 (LP64) */
+/* The inputs are read in place and never written.  The offsets and indices of the tables are trusted.  EINVAL: null args; a bit depth outside 8..16; geometry
+ * havoc_mi355x_cqt_decide refuses; n < 0; a null pointer other than d_cand_mv and the piece pointers; a stride that is not positive; a negative origin; a
+ * destination (d_rec_y, d_rec_c, d_cells) that is one of the inputs or another destination; d_cells, d_cand_mv, d_node or d_units not 8-byte aligned.  No allocation, no
+ * synchronisation, no workspace: capturable into a HIP graph. */
+int havoc_mi355x_cqt_commit(havoc_mi355x_ctx *ctx, const havoc_mi355x_cqt_commit_args *args);
+
 /* ---- an intra picture's partitions with their real dependencies (round 4; csrc/kernels_decide.hip) ----
  * A partition predicts from the reconstruction of what precedes it (turing/Reconstruct.cpp:609-615) and takes candModeList from its neighbours' decided modes
  * (turing/CandModeList.h:33-95).  A client that runs the batch chain over the partitions level by level (every partition of a level has all its neighbours final)

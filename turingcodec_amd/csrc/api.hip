@@ -35,6 +35,9 @@ static_assert(sizeof(havoc_mi355x_cu_close_job) == 32 && offsetof(havoc_mi355x_c
               sizeof(havoc_mi355x_rqt_choice) == 104 && sizeof(havoc_mi355x_rqt_tree_choice) == 16, "the coding-unit records are ABI");
 static_assert(sizeof(havoc_mi355x_cqt_ctu) == 40 && offsetof(havoc_mi355x_cqt_ctu, rate) == 8 && sizeof(havoc_mi355x_cqt_node) == 24 &&
               offsetof(havoc_mi355x_cqt_node, cost_full) == 8 && offsetof(havoc_mi355x_cu_choice, lambda_distortion) == 16, "the coding-quadtree records are ABI");
+static_assert(sizeof(havoc_mi355x_cqt_cell) == 24 && offsetof(havoc_mi355x_cqt_cell, mv) == 8 && offsetof(havoc_mi355x_cqt_cell, log2_size) == 16 &&
+              offsetof(havoc_mi355x_cqt_cell, cbf) == 20 && sizeof(havoc_mi355x_cqt_commit_args) == 288 && offsetof(havoc_mi355x_cqt_commit_args, d_units) == 24 &&
+              offsetof(havoc_mi355x_cqt_commit_args, luma_pieces) == 104 && offsetof(havoc_mi355x_cqt_commit_args, d_rec_y) == 224, "the quadtree commit records are ABI");
 static_assert(sizeof(havoc_mi355x_intra_rate_job) == 32 && offsetof(havoc_mi355x_intra_rate_job, scan_idx) == 12 && offsetof(havoc_mi355x_intra_rate_job, flags) == 15,
               "job ABI");
 static_assert(sizeof(havoc_mi355x_pred_select_job) == 32 && offsetof(havoc_mi355x_pred_select_job, log2_size) == 24, "job ABI");
@@ -1234,6 +1237,36 @@ int havoc_mi355x_cqt_decide(havoc_mi355x_ctx *ctx, int width, int height, int ct
     REQUIRE((bits & 7) == 0, "cqt_decide: every device pointer must be 8-byte aligned");
     return check(launch_cqt_decide(LS(ctx), width, height, ctb_log2, min_cb_log2, flags, d_cu_syntax, d_node_cu, d_choice, n_choice, d_work, d_ctu, d_node, d_depth,
                                    d_cu_syntax_out), "cqt_decide");
+}
+
+int havoc_mi355x_cqt_commit(havoc_mi355x_ctx *ctx, const havoc_mi355x_cqt_commit_args *args)
+{
+    REQUIRE_CTX();
+    REQUIRE(args != nullptr, "cqt_commit: null args");
+    const havoc_mi355x_cqt_commit_args &a = *args;
+    REQUIRE(a.bit_depth >= 8 && a.bit_depth <= 16, "cqt_commit: bit_depth must be 8..16");
+    REQUIRE(a.ctb_log2 >= 4 && a.ctb_log2 <= 6, "cqt_commit: ctb_log2 must be 4..6");
+    REQUIRE(a.min_cb_log2 >= 3 && a.min_cb_log2 <= a.ctb_log2, "cqt_commit: min_cb_log2 must be 3..ctb_log2");
+    REQUIRE(a.width > 0 && a.height > 0 && a.width % (1 << a.min_cb_log2) == 0 && a.height % (1 << a.min_cb_log2) == 0,
+            "cqt_commit: width and height must be positive multiples of the minimum coding block size");
+    REQUIRE(a.n >= 0, "cqt_commit: n < 0");
+    const void *ins[] = {a.d_units, a.d_node_cu, a.d_ctu, a.d_node, a.d_cu, a.d_choice, a.d_tree_choice, a.d_zero_at, a.d_one_at, a.d_chroma_at, a.d_pred_y, a.d_pred_c,
+                         a.d_pred_off, a.d_best, a.d_unit_cand};
+    const void *optional[] = {a.d_cand_mv, a.luma_pieces[0], a.luma_pieces[1], a.luma_pieces[2], a.luma_pieces[3], a.chroma_pieces[0], a.chroma_pieces[1], a.chroma_pieces[2]};
+    const void *outs[] = {a.d_rec_y, a.d_rec_c, a.d_cells};
+    for (const void *i : ins) REQUIRE(i != nullptr, "cqt_commit: null device pointer");
+    for (const void *o : outs) REQUIRE(o != nullptr, "cqt_commit: null device pointer");
+    REQUIRE(a.pred_stride > 0 && a.pred_stride_c > 0 && a.rec_stride > 0 && a.c_stride > 0, "cqt_commit: a stride must be positive");
+    REQUIRE(a.rec_origin >= 0 && a.cb_origin >= 0 && a.cr_origin >= 0, "cqt_commit: a negative origin");
+    for (int k = 0; k < 3; ++k)
+    {
+        for (const void *i : ins) REQUIRE(outs[k] != i, "cqt_commit: a destination must not be one of the inputs (which are never written)");
+        for (const void *i : optional) REQUIRE(outs[k] != i, "cqt_commit: a destination must not be one of the inputs (which are never written)");
+        for (int b = 0; b < k; ++b) REQUIRE(outs[k] != outs[b], "cqt_commit: the destinations must be distinct");
+    }
+    REQUIRE(((reinterpret_cast<uintptr_t>(a.d_cells) | reinterpret_cast<uintptr_t>(a.d_cand_mv) | reinterpret_cast<uintptr_t>(a.d_node) |
+              reinterpret_cast<uintptr_t>(a.d_units)) & 7) == 0, "cqt_commit: d_cells, d_cand_mv, d_node and d_units must be 8-byte aligned");
+    return check(launch_cqt_commit(LS(ctx), a), "cqt_commit");
 }
 
 } // extern "C"

@@ -16,6 +16,7 @@
 //           the word of CTU max(x + 1, min(1, cx - 1)) of the row above (the upper depths come from CTU x + 1, the row's start contexts from CTU 1), and reads the
 //           upper neighbours' CtDepth from the picture's map behind an acquire fence.  This keeps every global load off the chain.
 // A wait that gives up raises the give-up word; the rows below are let through and k_cqt_finish clears `decided` in every record of the call.
+// k_cqt_commit (below, with its own comment) acts on the decision: the final units of every decided CTU into one picture and a per-cell field.  DESIGN 7, row f2^8.
 #include "cabac_tables.h"
 #include "common.h"
 #include "launch.h"
@@ -397,7 +398,129 @@ __global__ __launch_bounds__(128) void k_cqt_decide(CqtArgs A, CqtWork wk, const
     }
 }
 
+// k_cqt_commit: acting on the decision -- the final coding units of every decided CTU into one picture of three planes and one record per MinCb cell (DESIGN 7, row
+// f2^8; the rule is restated in search/cqt_decision.hpp: commitCqt).  Nothing is computed: the samples were made by unit_pred_select and the tu_reconstruct launches of
+// the unit plan, this kernel selects.  k_unit_pred_select's form: a wavefront per SEARCHED unit, four per workgroup, no LDS; every decision is wave-uniform, and the
+// wavefront of a unit that is not committed -- most of them: the searched units overlap, the final ones tile the picture once -- returns after reading its unit, CTU,
+// node-table and node records.  Rows go round the lanes in 8-byte pieces (4-byte pieces for an 8-bit 4x4 block), plain vector loads and stores.
+// The final units of a CTU PARTITION it (test_cqt: the decided tree is a partition), and a unit is committed only as the node its own geometry names, so no two
+// wavefronts write the same sample or cell: no atomics, no order between wavefronts.
+using CommitArgs = havoc_mi355x_cqt_commit_args;
+
+// a (1 << log2)^2 block of S-byte samples; strides in bytes
+template <int S>
+__device__ __forceinline__ void copy_block(char *d, long sd, const char *a, long sa, int log2, int lane)
+{
+    const int rowBytes = S << log2;
+    if (rowBytes >= 8)
+    {
+        const int lp = __builtin_ctz(rowBytes) - 3, items = (1 << log2) << lp;     // pieces per row (a power of two), pieces of the block
+        for (int t = lane; t < items; t += 64)
+        {
+            const int y = t >> lp, x = (t & ((1 << lp) - 1)) * 8;
+            st8(d + y * sd + x, ld8(a + y * sa + x));
+        }
+    }
+    else if (lane < 4)      // 4 rows of 4 bytes
+        st4(d + lane * sd, ld4(a + lane * sa));
+}
+
+// a block of a plane from candidate pieces: one piece of size log2 (quads == false), or four of size log2 - 1 in z-order; `at` the (first) candidate's index
+template <int S>
+__device__ __forceinline__ void copy_pieces(char *d, long sd, const void *const *pieces, int log2, bool quads, int at, int lane)
+{
+    if (!quads)
+    {
+        copy_block<S>(d, sd, static_cast<const char *>(pieces[log2 - 2]) + ((long)at << 2 * log2) * S, S << log2, log2, lane);
+        return;
+    }
+    const int l = log2 - 1;
+    const char *a = static_cast<const char *>(pieces[l - 2]);
+#pragma unroll 1
+    for (int q = 0; q < 4; ++q)
+        copy_block<S>(d + ((long)(q >> 1) << l) * sd + ((long)(q & 1) << l) * S, sd, a + ((long)(at + q) << 2 * l) * S, S << l, l, lane);
+}
+
+template <int S>
+__global__ __launch_bounds__(256) void k_cqt_commit(CommitArgs A, int cx, int nodes)
+{
+    const int lane = threadIdx.x & 63, p = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (p >= A.n) return;       // wave-uniform, as every branch below
+    const havoc_mi355x_rqt_unit u = A.d_units[p];
+    const int L = u.log2_size, size = 1 << L, d = A.ctb_log2 - L;
+    if (L < A.min_cb_log2 || d < 0) return;
+    if (u.x0 < 0 || u.y0 < 0 || ((u.x0 | u.y0) & (size - 1)) || u.x0 + size > A.width || u.y0 + size > A.height) return;     // no such node: skipped, not followed
+    const int c = (u.y0 >> A.ctb_log2) * cx + (u.x0 >> A.ctb_log2);
+    if (A.d_ctu[c].decided != 1) return;
+    const int px = (u.x0 & ((1 << A.ctb_log2) - 1)) >> L, py = (u.y0 & ((1 << A.ctb_log2) - 1)) >> L;
+    int z = 0;
+#pragma unroll
+    for (int b = 0; b < 3; ++b) z |= (px >> b & 1) << 2 * b | (py >> b & 1) << (2 * b + 1);
+    const long at = (long)c * nodes + first_node(d) + z;
+    if (A.d_node_cu[at] != p) return;
+    const unsigned int node = (unsigned int)*reinterpret_cast<const unsigned long long *>(A.d_node + at);        // choice, flags, ctx_inc
+    if ((node & 255) != HAVOC_CQT_CU || !(node >> 8 & HAVOC_CQT_NODE_FINAL)) return;
+    const int outcome = A.d_cu[p].outcome;
+    if (outcome != HAVOC_CU_OUTCOME_CODED && outcome != HAVOC_CU_OUTCOME_NO_RESIDUAL && outcome != HAVOC_CU_OUTCOME_SKIPPED) return;
+
+    char *recY = static_cast<char *>(A.d_rec_y) + (A.rec_origin + (long)u.y0 * A.rec_stride + u.x0) * S;
+    const long cAt = (long)(u.y0 >> 1) * A.c_stride + (u.x0 >> 1), sdY = A.rec_stride * S, sdC = A.c_stride * S;
+    char *recCb = static_cast<char *>(A.d_rec_c) + (A.cb_origin + cAt) * S, *recCr = static_cast<char *>(A.d_rec_c) + (A.cr_origin + cAt) * S;
+    int trDepth = 0;
+    unsigned int cbf = 0;
+    if (outcome == HAVOC_CU_OUTCOME_CODED)
+    {   // the pieces of the depth that stands: cu_close's own rule; a 64x64 unit has its depth-1 pieces only
+        const havoc_mi355x_rqt_choice *ch = A.d_choice + p;
+        trDepth = (L < 6 && ch->depth == 0 && ch->tried_zero) ? 0 : 1;
+        const havoc_mi355x_rqt_tree_choice tc = A.d_tree_choice[p];
+        const havoc_mi355x_rqt_chroma_at ca = A.d_chroma_at[p];
+        cbf = trDepth ? tc.mask_one : tc.mask_zero;
+        copy_pieces<S>(recY, sdY, A.luma_pieces, L, trDepth != 0, trDepth ? A.d_one_at[p] : A.d_zero_at[p], lane);
+        const bool quads = trDepth != 0 && L > 3;       // an 8x8 unit's one 4x4 block per component serves both depths
+        copy_pieces<S>(recCb, sdC, A.chroma_pieces, L - 1, quads, quads ? ca.cb_one : ca.cb_zero, lane);
+        copy_pieces<S>(recCr, sdC, A.chroma_pieces, L - 1, quads, quads ? ca.cr_one : ca.cr_zero, lane);
+    }
+    else
+    {   // left at its prediction
+        const int32_t *off = A.d_pred_off + 3 * (long)p;
+        const char *predY = static_cast<const char *>(A.d_pred_y), *predC = static_cast<const char *>(A.d_pred_c);
+        copy_block<S>(recY, sdY, predY + (long)off[0] * S, A.pred_stride * S, L, lane);
+        copy_block<S>(recCb, sdC, predC + (long)off[1] * S, A.pred_stride_c * S, L - 1, lane);
+        copy_block<S>(recCr, sdC, predC + (long)off[2] * S, A.pred_stride_c * S, L - 1, lane);
+    }
+    // the unit's cells: at most 8 x 8, a lane each, three 8-byte stores
+    const int cl = L - A.min_cb_log2;
+    if (lane < 1 << 2 * cl)
+    {
+        const int pred = A.d_best[p] & 255, cand = A.d_unit_cand[p];
+        unsigned long long mv = 0;
+        if (A.d_cand_mv != nullptr && cand >= 0) mv = *reinterpret_cast<const unsigned long long *>(A.d_cand_mv + 4 * (long)cand);
+        if (pred != 0 && pred != 2) mv &= ~0xffffffffull;       // a list the mode does not use: 0, 0
+        if (pred != 1 && pred != 2) mv &= 0xffffffffull;
+        const long cell = (long)((u.y0 >> A.min_cb_log2) + (lane >> cl)) * (A.width >> A.min_cb_log2) + (u.x0 >> A.min_cb_log2) + (lane & ((1 << cl) - 1));
+        unsigned long long *o = reinterpret_cast<unsigned long long *>(A.d_cells + cell);
+        o[0] = (unsigned int)p | (unsigned long long)(unsigned int)cand << 32;
+        o[1] = mv;
+        o[2] = (unsigned long long)(L | outcome << 8 | pred << 16 | trDepth << 24) | (unsigned long long)cbf << 32;
+    }
+}
+
 } // namespace
+
+hipError_t launch_cqt_commit(hipStream_t st, const havoc_mi355x_cqt_commit_args &A)
+{
+    const int wc = A.width >> A.min_cb_log2, hc = A.height >> A.min_cb_log2;
+    const int cx = (A.width + (1 << A.ctb_log2) - 1) >> A.ctb_log2, levels = A.ctb_log2 - A.min_cb_log2 + 1;
+    // every cell "no unit" first: the cells of an undecided CTU stay so
+    hipError_t e = hipMemsetAsync(A.d_cells, 0xff, (size_t)wc * hc * sizeof(havoc_mi355x_cqt_cell), st);
+    if (e != hipSuccess || A.n <= 0) return e;
+    const dim3 grid((unsigned)((A.n + 3) / 4)), block(256);
+    if (A.bit_depth == 8)
+        hipLaunchKernelGGL(k_cqt_commit<1>, grid, block, 0, st, A, cx, ((1 << 2 * levels) - 1) / 3);
+    else
+        hipLaunchKernelGGL(k_cqt_commit<2>, grid, block, 0, st, A, cx, ((1 << 2 * levels) - 1) / 3);
+    return hipGetLastError();
+}
 
 size_t cqt_decide_workspace_bytes(int nctus) { return nctus <= 0 ? 0 : (size_t)nctus * 8 + 16; }
 

@@ -462,8 +462,10 @@ class DecisionPicture:
     PAD = 96
 
     def __init__(self, hv, width, height, bit_depth=8, qp=32, seed=11, threads=16, frames=None, density=1.0, intra=True, search_on_device=True, distance=1,
-                 sao=False, residual_rates=False, tree_rates=False, pu_modes=False, cu_close=False, cqt=False, unit_trees=False):
+                 sao=False, residual_rates=False, tree_rates=False, pu_modes=False, cu_close=False, cqt=False, unit_trees=False, commit=False):
         import torch
+        if commit and not (unit_trees and cqt):
+            raise ValueError("commit=True commits the quadtree decided over the searched units into one picture: it needs unit_trees=True and cqt=True")
         if unit_trees and not search_on_device:
             raise ValueError("unit_trees=True needs the device route (search_on_device=True)")
         if unit_trees and not (tree_rates and pu_modes and cu_close):
@@ -507,6 +509,9 @@ class DecisionPicture:
         # the tree, close and quadtree stages run over the SEARCHED units (self.pus), each with the transform tree of its own winning prediction (unit_pred_select,
         # a second tree plan, rqt_decide_units); the legacy plan over self.units still makes recon / crecon / cells, untouched
         self.unit_trees = unit_trees
+        # the decided quadtree acted on: its final units' samples into cqt_recon / cqt_crecon and one record per 8x8 cell into cqt_cells (havoc_mi355x_cqt_commit);
+        # recon / crecon / cells stay the legacy plan's
+        self.commit = commit
         self.sao = sao                                # in-loop SAO between deblocking and padding (sao_filter_inputs / sao_loop_filter)
         from . import havoc as hmod
         from . import workload
@@ -596,6 +601,9 @@ class DecisionPicture:
         self.d_field = hv.zeros(2 * ((width + 3) // 4) * ((height + 3) // 4) * 2, np.int16)
         self.layout = hv.field_layout(width, height, self.stride, self.PAD, self.pe, self.cstride, self.PAD // 2, self.cpe)
         self.crecon = hv.zeros(2 * self.cpe, self.dt)
+        if commit:          # the decided picture in buffers of its own, laid out as recon / crecon are; the cells: havoc.CQT_CELL_DT per MinCb cell
+            self.cqt_recon, self.cqt_crecon = hv.zeros(self.pe, self.dt), hv.zeros(2 * self.cpe, self.dt)
+            self.cqt_cells = hv.zeros((height >> self.CQT_MIN_CB_LOG2) * (width >> self.CQT_MIN_CB_LOG2) * hmod.CQT_CELL_DT.itemsize, np.uint8)
         # ---- the intra candidates of the picture (an inter picture evaluates them per coding unit): partitions with neighbours from the source
         self.intra_parts = {}
         self.rsl = float(self.params.reciprocal_sqrt_lambda)
@@ -835,6 +843,13 @@ class DecisionPicture:
                     bj[:, 3] = bj[:, 4] = size
                     q["d_uj"].copy_(torch.from_numpy(uj.reshape(-1)))
                     q["d_bj"].copy_(torch.from_numpy(bj.reshape(-1)))
+            if self.commit:     # every candidate's vectors [list][x, y] by its global index, for the cells of the committed units (a list it does not use: 0, 0)
+                cand_mv = np.zeros((P["M"], 2, 2), np.int16)
+                cand_mv[first, 0], cand_mv[first + 1, 1], cand_mv[first + 2] = uni_mv[:, 0], uni_mv[:, 1], bi_mv
+                if "d_cand_mv" not in P:
+                    P["d_cand_mv"] = hv.zeros(cand_mv.size, np.int16)
+                P["cand_mv"] = cand_mv
+                P["d_cand_mv"].copy_(torch.from_numpy(cand_mv.reshape(-1)))
         self._pu_decisions = None
 
     def pu_mode_launches(self):
@@ -990,6 +1005,33 @@ class DecisionPicture:
             self._cqt_decisions = dict(node_cu=B["node_cu"], gave_up=bool(work[self.cx * self.cy] >> 32),
                                        **self.hv.cqt_download(B, self.W, self.H, self.CQT_CTB_LOG2, self.CQT_MIN_CB_LOG2))
         return self._cqt_decisions
+
+    # ---- acting on the decision: the final units of every decided CTU into one picture and a per-cell field (havoc_mi355x_cqt_commit) ----------------------------
+    def cqt_commit_launch(self):
+        """behind cqt_launch: of the searched units the final coding units of the decided quadtrees -- a unit left without residual or skipped as its block of the unit
+        prediction planes, a coded unit as the candidate pieces of the transform depth that stands -- into cqt_recon / cqt_crecon, and cqt_cells.  Everything is read
+        where the launches before left it.  One call (a fill and a launch); asynchronous"""
+        hv, P, U, Q, B = self.hv, self._pu_plan(), self._unit_tree_plan(), self._cu_plan(), self._cqt_plan()
+        if "d_pred_off" not in U:
+            U["d_pred_off"] = hv.up(np.ascontiguousarray(U["select_jobs"]["dst_off"], np.int32).reshape(-1))
+        piece = lambda groups, sizes: [groups[s]["piece"] if s in groups else None for s in sizes]
+        hv.cqt_commit_d(self.bd, self.W, self.H, self.CQT_CTB_LOG2, self.CQT_MIN_CB_LOG2, U["d_units"], B["d_node_cu"], B["ctu"], B["node"], Q["d_out"], U["d_out"],
+                        U["d_tree_out"], U["d_zero_at"], U["d_one_at"], U["d_chroma_at"], piece(U["sizes"], (2, 3, 4, 5)), piece(U["csizes"], (2, 3, 4)), U["pred"],
+                        self.W, U["cpred"], self.W // 2, U["d_pred_off"], P["d_best"], U["d_unit_cand"], P["d_cand_mv"], self.cqt_recon, self.origin, self.stride,
+                        self.cqt_crecon, self.corigin, self.cpe + self.corigin, self.cstride, self.cqt_cells)
+
+    def cqt_commit_results(self):
+        """what cqt_commit_launch() left on the device, as numpy, cropped to the picture: dict(recon dt [H, W], crecon dt [2, H / 2, W / 2], cells (havoc.CQT_CELL_DT
+        [H / 8, W / 8]: unit -1 in an undecided CTU))"""
+        if not self.commit:
+            raise ValueError("cqt_commit_results: the picture was made without commit=True")
+        if getattr(self, "_cqt_commit", None) is None:
+            hv, pad, c2 = self.hv, self.PAD, self.PAD // 2
+            y = hv.down(self.cqt_recon, self.dt)[:self.n].reshape(-1, self.stride)[pad:pad + self.H, pad:pad + self.W]
+            c = hv.down(self.cqt_crecon, self.dt)
+            c = np.stack([c[k * self.cpe:k * self.cpe + self.cn].reshape(-1, self.cstride)[c2:c2 + self.H // 2, c2:c2 + self.W // 2] for k in range(2)])
+            self._cqt_commit = dict(recon=y.copy(), crecon=c, cells=hv.cqt_cells_download(self.cqt_cells, self.W, self.H, self.CQT_MIN_CB_LOG2))
+        return self._cqt_commit
 
     def chroma_chain(self, field):
         """the inter residual of the chroma planes at the decided vectors (turing/Reconstruct.cpp:1274-1286 with cIdx 1, 2): HavocPredUni 4-tap of every unit's
@@ -1658,11 +1700,12 @@ class DecisionPicture:
             # everything after the searches is a FIXED sequence of launches over device-resident tables (the decided field never leaves the device, the decisions
             # between the launches are kernels): recorded once into a HIP graph, one launch per picture, one wait at the end
             self._rqt = self._cells = self._sao_decisions = self._rqt_rates = self._rqt_tree = self._cu_decisions = self._cqt_decisions = None
-            self._unit_tree_decisions = None
+            self._unit_tree_decisions = self._cqt_commit = None
             pu = (self.pu_mode_launches,) if self.pu_modes else ()      # (the tables its launches read went up before the replay: pu_candidates)
             pu += (self.unit_tree_launches,) if self.unit_trees else ()  # (behind pu_decide: it reads the winners in place; before cu_close, which reads its records)
             pu += (self.cu_close_launches,) if self.cu_close else ()     # (after the tree decisions AND the prediction units' rates: it reads both in place)
             pu += (self.cqt_launch,) if self.cqt else ()                 # (behind cu_close: it reads its records in place)
+            pu += (self.cqt_commit_launch,) if self.commit else ()       # (directly behind the quadtree: it acts on its records, into buffers of its own)
             if self.sao:
                 self._replayed("after the searches", lambda: (self.merge_candidates(field), self.predict(field), self.sao_filter_inputs(field),
                                                               self.sao_loop_filter(), [f() for f in pu]))

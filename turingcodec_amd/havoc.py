@@ -137,6 +137,7 @@ def _load():
         "unit_pred_ssd": [_vp, _i, _vp, C.c_ssize_t, _vp, C.c_ssize_t, _vp, C.c_ssize_t, _vp, C.c_ssize_t, _vp, _i, _vp],
         "unit_pred_select": [_vp, _i, _vp, _vp, _vp, C.c_ssize_t, _vp, C.c_ssize_t, _vp, _vp, _vp, _vp, _i, _vp, _vp],
         "cqt_decide": [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, C.c_size_t, _vp, _vp, _vp, _vp],
+        "cqt_commit": [_vp, _vp],
         "intra_decide_rated": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_int32, _vp, _vp],
         "rqt_decide_rated": [_vp, _vp, _i, _vp, _vp, _vp, _vp, C.c_int64, C.c_ssize_t, _i, _i, _vp],
         "rqt_decide_tree": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_ssize_t, _i, C.c_int64, C.c_int64, C.c_ssize_t, _i, _i, _vp, _vp],
@@ -360,6 +361,21 @@ assert CQT_CTU_DT.itemsize == 40 and CQT_NODE_DT.itemsize == 24
 CQT_WPP, CQT_ECU = 1, 2
 CQT_NOT_VISITED, CQT_CU, CQT_SPLIT, CQT_DELETED = 0, 1, 2, 3
 CQT_NODE_FINAL, CQT_NODE_FLAG_CODED, CQT_NODE_MUST_SPLIT, CQT_NODE_ECU_STOP, CQT_NODE_NO_CANDIDATE, CQT_NODE_NO_SPLIT_CANDIDATE = 1, 2, 4, 8, 16, 32
+# one havoc_mi355x_cqt_cell (include/havoc_mi355x.h), 24 bytes: the decided coding unit that covers a MinCb cell; all-ones bytes (unit -1): none
+CQT_CELL_DT = np.dtype([("unit", "<i4"), ("cand", "<i4"), ("mv", "<i2", (2, 2)), ("log2_size", "u1"), ("outcome", "u1"), ("pred", "u1"), ("tr_depth", "u1"), ("cbf", "<u4")])
+assert CQT_CELL_DT.itemsize == 24
+
+
+class CqtCommitArgs(C.Structure):
+    """havoc_mi355x_cqt_commit_args: what havoc_mi355x_cqt_commit reads in place and where the decided picture and its cells go"""
+    _fields_ = ([(k, C.c_int32) for k in ("bit_depth", "width", "height", "ctb_log2", "min_cb_log2", "n")] +
+                [(k, _vp) for k in ("d_units", "d_node_cu", "d_ctu", "d_node", "d_cu", "d_choice", "d_tree_choice", "d_zero_at", "d_one_at", "d_chroma_at")] +
+                [("luma_pieces", _vp * 4), ("chroma_pieces", _vp * 3), ("d_pred_y", _vp), ("d_pred_c", _vp), ("pred_stride", _ip), ("pred_stride_c", _ip),
+                 ("d_pred_off", _vp), ("d_best", _vp), ("d_unit_cand", _vp), ("d_cand_mv", _vp), ("d_rec_y", _vp), ("rec_origin", C.c_int64), ("rec_stride", _ip),
+                 ("d_rec_c", _vp), ("cb_origin", C.c_int64), ("cr_origin", C.c_int64), ("c_stride", _ip), ("d_cells", _vp)])
+
+
+assert C.sizeof(CqtCommitArgs) == 288
 
 
 def cqt_nodes(ctb_log2, min_cb_log2):
@@ -1122,6 +1138,31 @@ class Havoc:
         B = self.cqt_buffers(width, height, ctb_log2, min_cb_log2)
         self.cqt_decide_d(width, height, ctb_log2, min_cb_log2, flags, ins[0], ins[1], ins[2], B["work"], B["ctu"], B["node"], B["depth"], B["cu_syntax_out"])
         return self.cqt_download(B, width, height, ctb_log2, min_cb_log2)
+
+    def cqt_commit_d(self, bit_depth, width, height, ctb_log2, min_cb_log2, units, node_cu, ctu, node, cu, choice, tree_choice, zero_at, one_at, chroma_at, luma_pieces,
+                     chroma_pieces, pred_y, pred_stride, pred_c, pred_stride_c, pred_off, best, unit_cand, cand_mv, rec_y, rec_origin, rec_stride, rec_c, cb_origin,
+                     cr_origin, c_stride, cells):
+        """the decided quadtree's final coding units into one picture and one CQT_CELL_DT record per MinCb cell (havoc_mi355x_cqt_commit), over what the calls before
+        left on the device, read in place: units int32 [n, 4]; node_cu, ctu, node: cqt_decide_d's; cu: cu_close_d's records; choice, tree_choice, zero_at, one_at,
+        chroma_at: rqt_decide_units_d's; luma_pieces / chroma_pieces: 4 / 3 tensors or None (transform sizes 2..5 / 2..4); pred_y, pred_c, pred_off int32 [n, 3]: the
+        unit prediction planes and each unit's block in them; best, unit_cand int32 [n]; cand_mv int16 [candidates, 2, 2] or None; cells: uint8 tensor of
+        (height >> min_cb_log2) * (width >> min_cb_log2) records.  No sync."""
+        a = CqtCommitArgs()
+        a.bit_depth, a.width, a.height, a.ctb_log2, a.min_cb_log2, a.n = int(bit_depth), int(width), int(height), int(ctb_log2), int(min_cb_log2), units.numel() // 4
+        for k, t in (("d_units", units), ("d_node_cu", node_cu), ("d_ctu", ctu), ("d_node", node), ("d_cu", cu), ("d_choice", choice), ("d_tree_choice", tree_choice),
+                     ("d_zero_at", zero_at), ("d_one_at", one_at), ("d_chroma_at", chroma_at), ("d_pred_y", pred_y), ("d_pred_c", pred_c), ("d_pred_off", pred_off),
+                     ("d_best", best), ("d_unit_cand", unit_cand), ("d_cand_mv", cand_mv), ("d_rec_y", rec_y), ("d_rec_c", rec_c), ("d_cells", cells)):
+            setattr(a, k, _ptr(t))
+        a.luma_pieces = (_vp * 4)(*[_ptr(t) for t in luma_pieces])
+        a.chroma_pieces = (_vp * 3)(*[_ptr(t) for t in chroma_pieces])
+        a.pred_stride, a.pred_stride_c, a.rec_stride, a.c_stride = int(pred_stride), int(pred_stride_c), int(rec_stride), int(c_stride)
+        a.rec_origin, a.cb_origin, a.cr_origin = int(rec_origin), int(cb_origin), int(cr_origin)
+        self._ck(self.L.havoc_mi355x_cqt_commit(self.h, C.addressof(a)))
+
+    def cqt_cells_download(self, cells, width, height, min_cb_log2):
+        """cqt_commit_d's cell map as numpy: CQT_CELL_DT [height >> min_cb_log2, width >> min_cb_log2]"""
+        hc, wc = height >> min_cb_log2, width >> min_cb_log2
+        return self.down(cells, np.uint8)[:hc * wc * CQT_CELL_DT.itemsize].view(CQT_CELL_DT).reshape(hc, wc).copy()
 
     def unit_pred_ssd_d(self, bit_depth, src_y, src_stride, src_c, src_stride_c, pred_y, pred_stride, pred_c, pred_stride_c, jobs, out):
         """SSD(source, prediction) of units' luma, Cb and Cr blocks in one launch (havoc_mi355x_unit_pred_ssd); jobs: uint8 tensor of PRED_SSD_JOB_DT; out: int32 [3 n].

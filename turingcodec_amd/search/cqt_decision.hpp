@@ -214,4 +214,119 @@ inline CqtCtu decideCqt(const CqtCandidate *cand, const int32_t *bins, const Cqt
     return out;
 }
 
+// ---- acting on the decision: the final coding units of one CTU into the picture and the per-cell field.  havoc_mi355x_cqt_commit does this for every CTU of a
+// picture in one launch, byte for byte; this is its host form, data-only: every sample was made before (the winner's prediction of each searched unit, the candidate
+// pieces of both transform depths), commitCqt selects.  What the reference's picture holds after Search<coding_quadtree>::go kept the CTU's winner (turing/Search.hpp:
+// 808-886 over :2362-2568): a unit left without residual or skipped is its prediction, a coded unit the reconstruction of the transform depth that stands.
+struct CqtCommitUnit { int32_t x0, y0, log2Size, ctxIndex; };       // a searched unit (= havoc_mi355x_rqt_unit)
+struct CqtCommitTree        // what is read of a unit's transform-tree records
+{
+    int32_t depth, triedZero;           // rqt_decide_units': the depth that stands is (log2Size < 6 && depth == 0 && triedZero) ? 0 : 1
+    uint32_t maskZero, maskOne;         // the trees' cbf masks
+    int32_t zeroAt, oneAt;              // the luma candidates: one of size log2Size, the first of four of size log2Size - 1
+    int32_t cbZero, crZero, cbOne, crOne;   // the chroma candidates: one of size log2Size - 1, the first of four of size log2Size - 2 (an 8x8 unit: cbZero / crZero only)
+};
+struct CqtCommitCell        // = havoc_mi355x_cqt_cell, 24 bytes
+{
+    int32_t unit, cand;
+    int16_t mv[2][2];
+    uint8_t log2Size, outcome, pred, trDepth;
+    uint32_t cbf;
+};
+template <class Sample>
+struct CqtCommit
+{
+    int width, height, ctbLog2, minCbLog2, n;
+    const CqtCommitUnit *units;         // [n]; index p means the same unit in every table
+    const int32_t *outcome;             // the close's: -1 refused, 0 coded, 1 no residual, 2 skipped
+    const CqtCommitTree *tree;
+    const Sample *lumaPieces[4];        // transform sizes 2..5: candidate j of size s is the contiguous block at j << 2 s
+    const Sample *chromaPieces[3];      // 2..4
+    const Sample *predY, *predC;        // the unit prediction planes
+    long predStride, predStrideC;
+    const int32_t *predOff;             // [n][3]: a unit's block in predY; in predC for Cb, Cr
+    const int32_t *best, *unitCand;     // the winning mode (0 L0, 1 L1, 2 bi) and candidate
+    const int16_t *candMv;              // [candidates][2 lists][x, y], or null: zero vectors
+    Sample *recY;
+    long recOrigin, recStride;
+    Sample *recC;
+    long cbOrigin, crOrigin, cStride;
+    CqtCommitCell *cells;               // one per MinCb cell of the picture; a cell no unit covers is the caller's (all-ones bytes)
+};
+
+template <class Sample>
+inline void cqtCopyBlock(Sample *d, long sd, const Sample *a, long sa, int log2)
+{
+    for (int y = 0; y < 1 << log2; ++y)
+        for (int x = 0; x < 1 << log2; ++x) d[y * sd + x] = a[y * sa + x];
+}
+
+// one piece of size log2, or four of size log2 - 1 in z-order
+template <class Sample>
+inline void cqtCopyPieces(Sample *d, long sd, const Sample *const *pieces, int log2, bool quads, int at)
+{
+    if (!quads)
+    {
+        cqtCopyBlock(d, sd, pieces[log2 - 2] + (long(at) << 2 * log2), 1l << log2, log2);
+        return;
+    }
+    const int l = log2 - 1;
+    for (int q = 0; q < 4; ++q) cqtCopyBlock(d + (long(q >> 1) << l) * sd + (long(q & 1) << l), sd, pieces[l - 2] + (long(at + q) << 2 * l), 1l << l, l);
+}
+
+// ctu: raster index; nodeCu, node: the CTU's cqtNodes(levels) entries as decideCqt read and wrote them.  Unit p = nodeCu[k] is committed when node k is final with
+// choice kCqtCu, p's own origin and size name node k of this CTU, and its outcome is one of the three that are not refused.  -> the units committed
+template <class Sample>
+inline int commitCqt(const CqtCommit<Sample> &P, int ctu, bool decided, const int32_t *nodeCu, const CqtNode *node)
+{
+    if (!decided) return 0;
+    const int levels = P.ctbLog2 - P.minCbLog2 + 1, count = cqtNodes(levels), cx = (P.width + (1 << P.ctbLog2) - 1) >> P.ctbLog2;
+    int done = 0;
+    for (int k = 0; k < count; ++k)
+    {
+        const int p = nodeCu[k];
+        if (p < 0 || p >= P.n || !(node[k].flags & kCqtFinal) || node[k].choice != kCqtCu) continue;
+        const CqtCommitUnit &u = P.units[p];
+        const int L = u.log2Size, size = 1 << L, d = P.ctbLog2 - L;
+        if (L < P.minCbLog2 || d < 0) continue;
+        if (u.x0 < 0 || u.y0 < 0 || ((u.x0 | u.y0) & (size - 1)) || u.x0 + size > P.width || u.y0 + size > P.height) continue;
+        const int px = (u.x0 & ((1 << P.ctbLog2) - 1)) >> L, py = (u.y0 & ((1 << P.ctbLog2) - 1)) >> L;
+        int z = 0;
+        for (int b = 0; b < 3; ++b) z |= (px >> b & 1) << 2 * b | (py >> b & 1) << (2 * b + 1);
+        if ((u.y0 >> P.ctbLog2) * cx + (u.x0 >> P.ctbLog2) != ctu || cqtFirst(d) + z != k) continue;
+        const int outcome = P.outcome[p];
+        if (outcome < 0 || outcome > 2) continue;
+        Sample *recY = P.recY + P.recOrigin + long(u.y0) * P.recStride + u.x0;
+        const long cAt = long(u.y0 >> 1) * P.cStride + (u.x0 >> 1);
+        int trDepth = 0;
+        uint32_t cbf = 0;
+        if (outcome == 0)
+        {
+            const CqtCommitTree &t = P.tree[p];
+            trDepth = (L < 6 && t.depth == 0 && t.triedZero) ? 0 : 1;
+            cbf = trDepth ? t.maskOne : t.maskZero;
+            cqtCopyPieces(recY, P.recStride, P.lumaPieces, L, trDepth != 0, trDepth ? t.oneAt : t.zeroAt);
+            const bool quads = trDepth != 0 && L > 3;
+            cqtCopyPieces(P.recC + P.cbOrigin + cAt, P.cStride, P.chromaPieces, L - 1, quads, quads ? t.cbOne : t.cbZero);
+            cqtCopyPieces(P.recC + P.crOrigin + cAt, P.cStride, P.chromaPieces, L - 1, quads, quads ? t.crOne : t.crZero);
+        }
+        else
+        {
+            const int32_t *off = P.predOff + 3 * long(p);
+            cqtCopyBlock(recY, P.recStride, P.predY + off[0], P.predStride, L);
+            cqtCopyBlock(P.recC + P.cbOrigin + cAt, P.cStride, P.predC + off[1], P.predStrideC, L - 1);
+            cqtCopyBlock(P.recC + P.crOrigin + cAt, P.cStride, P.predC + off[2], P.predStrideC, L - 1);
+        }
+        CqtCommitCell cell = {p, P.unitCand[p], {{0, 0}, {0, 0}}, uint8_t(L), uint8_t(outcome), uint8_t(P.best[p]), uint8_t(trDepth), cbf};
+        if (P.candMv && cell.cand >= 0)
+            for (int l = 0; l < 2; ++l)
+                if (cell.pred == l || cell.pred == 2) cell.mv[l][0] = P.candMv[4 * long(cell.cand) + 2 * l], cell.mv[l][1] = P.candMv[4 * long(cell.cand) + 2 * l + 1];
+        const int cl = L - P.minCbLog2, wc = P.width >> P.minCbLog2;
+        for (int j = 0; j < 1 << cl; ++j)
+            for (int i = 0; i < 1 << cl; ++i) P.cells[long((u.y0 >> P.minCbLog2) + j) * wc + (u.x0 >> P.minCbLog2) + i] = cell;
+        ++done;
+    }
+    return done;
+}
+
 } // namespace havoc_search
