@@ -1234,6 +1234,28 @@ typedef struct {
  * synchronisation, no workspace: capturable into a HIP graph. */
 int havoc_mi355x_cqt_commit(havoc_mi355x_ctx *ctx, const havoc_mi355x_cqt_commit_args *args);
 
+/* ---- the committed cells as the loop filter's block structure (csrc/kernels_cqt.hip: k_cqt_block_cells) ----
+ * The translation between havoc_mi355x_cqt_commit's record per MinCb cell and the map of 4x4 havoc_mi355x_cell records havoc_mi355x_derive_bs reads: what
+ * LoopFilter::Picture::processCu / processPu / processTu / processRc see of the decided picture (turing/LoopFilter.h:541-737), every coding unit one inter 2Nx2N
+ * prediction unit.  Behind it havoc_mi355x_derive_bs, havoc_mi355x_deblock and havoc_mi355x_pad_block leave in the committed planes what TaskDeblock.cpp:105-167
+ * leaves before the picture is used for prediction.
+ * Writes EVERY cell of the (height / 4) x (width / 4) map, rows cells_stride cells apart, once; the bytes between the rows are not touched.  The 4x4 cell at luma
+ * position (x, y) reads q = d_cqt_cells[(y >> min_cb_log2) * (width >> min_cb_log2) + (x >> min_cb_log2)]:
+ *   - q.unit < 0 (an undecided CTU: all-ones bytes): mv 0, dpb_index {-1, -1}, flags = HAVOC_CELL_NO_FILTER (the samples are nobody's: the filter leaves them alone),
+ *     qp_y = qp, tu_log2 = 2, reserved 0; no other field of q is read;
+ *   - otherwise, with size = 1 << q.log2_size, ox = x & (size - 1), oy = y & (size - 1) (a coding unit is aligned to its size):
+ *       mv = q.mv, both lists as stored;  dpb_index[0] = q.pred != 1 ? dpb_index0 : -1;  dpb_index[1] = q.pred != 0 ? dpb_index1 : -1;
+ *       tu_log2 = min(q.log2_size - q.tr_depth, 5)  (a 64x64 unit: 5 either way -- its split is inferred when coded, and the clamp applies when nothing is);
+ *       k = q.tr_depth ? (oy >= size / 2) * 2 + (ox >= size / 2) : 0;  HAVOC_CELL_CODED exactly when q.outcome == HAVOC_CU_OUTCOME_CODED && (q.cbf >> k & 1)
+ *       (bits 0..3 of the mask: the luma blocks, as havoc_mi355x_tree_rate documents);  HAVOC_CELL_PU_LEFT when ox == 0, HAVOC_CELL_PU_TOP when oy == 0;
+ *       never HAVOC_CELL_INTRA;  qp_y = qp, reserved 0.  cand, unit beyond its sign and the chroma bits of cbf are not read.
+ * Argument order: ctx, width, height, min_cb_log2, qp, dpb_index0, dpb_index1, d_cqt_cells (in), d_cells (out), cells_stride.
+ * The input is trusted and never written.  EINVAL: a null pointer; min_cb_log2 outside 3..6; a width or height that is not a positive multiple of 1 << min_cb_log2;
+ * qp outside 0..51; a dpb index outside 0..127; cells_stride < width / 4; d_cells == d_cqt_cells; d_cqt_cells not 8-byte aligned or d_cells not 16-byte aligned.
+ * One launch; no allocation, no synchronisation, no workspace: capturable into a HIP graph. */
+int havoc_mi355x_cqt_block_cells(havoc_mi355x_ctx *ctx, int width, int height, int min_cb_log2, int qp, int dpb_index0, int dpb_index1,
+                                 const havoc_mi355x_cqt_cell *d_cqt_cells, havoc_mi355x_cell *d_cells, intptr_t cells_stride);
+
 /* ---- an intra picture's partitions with their real dependencies (round 4; csrc/kernels_decide.hip) ----
  * A partition predicts from the reconstruction of what precedes it (turing/Reconstruct.cpp:609-615) and takes candModeList from its neighbours' decided modes
  * (turing/CandModeList.h:33-95).  A client that runs the batch chain over the partitions level by level (every partition of a level has all its neighbours final)

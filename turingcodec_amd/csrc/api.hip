@@ -1269,4 +1269,22 @@ int havoc_mi355x_cqt_commit(havoc_mi355x_ctx *ctx, const havoc_mi355x_cqt_commit
     return check(launch_cqt_commit(LS(ctx), a), "cqt_commit");
 }
 
+int havoc_mi355x_cqt_block_cells(havoc_mi355x_ctx *ctx, int width, int height, int min_cb_log2, int qp, int dpb_index0, int dpb_index1,
+                                 const havoc_mi355x_cqt_cell *d_cqt_cells, havoc_mi355x_cell *d_cells, intptr_t cells_stride)
+{
+    REQUIRE_CTX();
+    REQUIRE(d_cqt_cells != nullptr && d_cells != nullptr, "cqt_block_cells: null device pointer");
+    REQUIRE(min_cb_log2 >= 3 && min_cb_log2 <= 6, "cqt_block_cells: min_cb_log2 must be 3..6");
+    REQUIRE(width > 0 && height > 0 && width % (1 << min_cb_log2) == 0 && height % (1 << min_cb_log2) == 0,
+            "cqt_block_cells: width and height must be positive multiples of the minimum coding block size");
+    REQUIRE(qp >= 0 && qp <= 51, "cqt_block_cells: qp must be 0..51");
+    REQUIRE(dpb_index0 >= 0 && dpb_index0 <= 127 && dpb_index1 >= 0 && dpb_index1 <= 127, "cqt_block_cells: a dpb index must be 0..127");
+    REQUIRE(cells_stride >= width / 4, "cqt_block_cells: cells_stride must be at least width / 4");
+    REQUIRE(static_cast<const void *>(d_cells) != static_cast<const void *>(d_cqt_cells), "cqt_block_cells: the destination must not be the input (which is never written)");
+    REQUIRE((reinterpret_cast<uintptr_t>(d_cqt_cells) & 7) == 0 && (reinterpret_cast<uintptr_t>(d_cells) & 15) == 0,
+            "cqt_block_cells: d_cqt_cells must be 8-byte aligned, d_cells 16-byte aligned");
+    REQUIRE((long long)(width >> 2) * (height >> 2) < (1ll << 31) - 256, "cqt_block_cells: too many cells");
+    return check(launch_cqt_block_cells(LS(ctx), width, height, min_cb_log2, qp, dpb_index0, dpb_index1, d_cqt_cells, d_cells, cells_stride), "cqt_block_cells");
+}
+
 } // extern "C"

@@ -17,6 +17,7 @@
 //           upper neighbours' CtDepth from the picture's map behind an acquire fence.  This keeps every global load off the chain.
 // A wait that gives up raises the give-up word; the rows below are let through and k_cqt_finish clears `decided` in every record of the call.
 // k_cqt_commit (below, with its own comment) acts on the decision: the final units of every decided CTU into one picture and a per-cell field.  DESIGN 7, row f2^8.
+// k_cqt_block_cells (below) turns that field into the 4x4 cells the loop filter's boundary strengths are derived from.  DESIGN 7, row f2^9.
 #include "cabac_tables.h"
 #include "common.h"
 #include "launch.h"
@@ -505,6 +506,31 @@ __global__ __launch_bounds__(256) void k_cqt_commit(CommitArgs A, int cx, int no
     }
 }
 
+// k_cqt_block_cells: the 4x4 cells havoc_mi355x_derive_bs reads, made from the committed 8x8 (MinCb) cells (DESIGN 7, row f2^9; the rule is stated in
+// include/havoc_mi355x.h and restated in search/cqt_decision.hpp: cqtBlockCells).  A lane per OUTPUT cell in raster order: three aligned 8-byte loads of the record
+// that covers it (the lanes of one MinCb cell read the same lines), every branch a select, one aligned 16-byte store -- a wavefront writes 1 KB contiguous when the
+// rows are dense.  A coding unit is aligned to its size, so the cell's own position names the unit's origin: no unit table, no second pass, every cell written once.
+__global__ __launch_bounds__(256) void k_cqt_block_cells(const havoc_mi355x_cqt_cell *__restrict__ q, int cw, int count, int minCbLog2, int qcw, int qp, int dpb0, int dpb1,
+                                                         havoc_mi355x_cell *__restrict__ cells, long stride)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    const int cy = i / cw, cx = i - cy * cw, x = cx << 2, y = cy << 2;
+    const unsigned long long *r = reinterpret_cast<const unsigned long long *>(q + (long)(y >> minCbLog2) * qcw + (x >> minCbLog2));
+    const unsigned long long head = r[0], mv = r[1], tail = r[2];
+    const bool decided = (int)(unsigned int)head >= 0;          // unit -1: the commit left all-ones bytes, nothing else of the record means anything
+    const unsigned int info = (unsigned int)tail, cbf = (unsigned int)(tail >> 32);
+    const int L = decided ? (int)(info & 255) : 3, outcome = info >> 8 & 255, pred = info >> 16 & 255, depth = info >> 24 & 255;
+    const int size = 1 << L, ox = x & (size - 1), oy = y & (size - 1), half = size >> 1;
+    const int k = depth ? (oy >= half) * 2 + (ox >= half) : 0;
+    const bool coded = outcome == HAVOC_CU_OUTCOME_CODED && (cbf >> k & 1);
+    const unsigned int flags = decided ? (coded ? HAVOC_CELL_CODED : 0) | (ox == 0 ? HAVOC_CELL_PU_LEFT : 0) | (oy == 0 ? HAVOC_CELL_PU_TOP : 0) : HAVOC_CELL_NO_FILTER;
+    const unsigned int d0 = decided && pred != 1 ? (unsigned int)dpb0 : 255u, d1 = decided && pred != 0 ? (unsigned int)dpb1 : 255u;
+    const unsigned int tu = decided ? (unsigned int)min(L - depth, 5) : 2u;
+    const unsigned long long v = decided ? mv : 0ull;
+    *reinterpret_cast<u32x4 *>(cells + (long)cy * stride + cx) = u32x4{(unsigned int)v, (unsigned int)(v >> 32), d0 | d1 << 8 | flags << 16 | (unsigned int)qp << 24, tu};
+}
+
 } // namespace
 
 hipError_t launch_cqt_commit(hipStream_t st, const havoc_mi355x_cqt_commit_args &A)
@@ -519,6 +545,15 @@ hipError_t launch_cqt_commit(hipStream_t st, const havoc_mi355x_cqt_commit_args 
         hipLaunchKernelGGL(k_cqt_commit<1>, grid, block, 0, st, A, cx, ((1 << 2 * levels) - 1) / 3);
     else
         hipLaunchKernelGGL(k_cqt_commit<2>, grid, block, 0, st, A, cx, ((1 << 2 * levels) - 1) / 3);
+    return hipGetLastError();
+}
+
+hipError_t launch_cqt_block_cells(hipStream_t st, int width, int height, int minCbLog2, int qp, int dpb0, int dpb1, const havoc_mi355x_cqt_cell *cqtCells,
+                                  havoc_mi355x_cell *cells, long stride)
+{
+    const int cw = width >> 2, count = cw * (height >> 2);
+    hipLaunchKernelGGL(k_cqt_block_cells, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, cqtCells, cw, count, minCbLog2, width >> minCbLog2, qp, dpb0, dpb1, cells,
+                       stride);
     return hipGetLastError();
 }
 

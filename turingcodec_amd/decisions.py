@@ -462,8 +462,10 @@ class DecisionPicture:
     PAD = 96
 
     def __init__(self, hv, width, height, bit_depth=8, qp=32, seed=11, threads=16, frames=None, density=1.0, intra=True, search_on_device=True, distance=1,
-                 sao=False, residual_rates=False, tree_rates=False, pu_modes=False, cu_close=False, cqt=False, unit_trees=False, commit=False):
+                 sao=False, residual_rates=False, tree_rates=False, pu_modes=False, cu_close=False, cqt=False, unit_trees=False, commit=False, finish=False):
         import torch
+        if finish and not commit:
+            raise ValueError("finish=True deblocks and pads the committed picture: it needs commit=True")
         if commit and not (unit_trees and cqt):
             raise ValueError("commit=True commits the quadtree decided over the searched units into one picture: it needs unit_trees=True and cqt=True")
         if unit_trees and not search_on_device:
@@ -512,6 +514,9 @@ class DecisionPicture:
         # the decided quadtree acted on: its final units' samples into cqt_recon / cqt_crecon and one record per 8x8 cell into cqt_cells (havoc_mi355x_cqt_commit);
         # recon / crecon / cells stay the legacy plan's
         self.commit = commit
+        # ... and finished as TaskDeblock.cpp:105-167 finishes a picture before it is used for prediction: the committed cells as 4x4 cells (havoc_mi355x_cqt_block_cells),
+        # boundary strengths, deblocking of cqt_recon / cqt_crecon in place, padding of the three planes
+        self.finish = finish
         self.sao = sao                                # in-loop SAO between deblocking and padding (sao_filter_inputs / sao_loop_filter)
         from . import havoc as hmod
         from . import workload
@@ -604,6 +609,10 @@ class DecisionPicture:
         if commit:          # the decided picture in buffers of its own, laid out as recon / crecon are; the cells: havoc.CQT_CELL_DT per MinCb cell
             self.cqt_recon, self.cqt_crecon = hv.zeros(self.pe, self.dt), hv.zeros(2 * self.cpe, self.dt)
             self.cqt_cells = hv.zeros((height >> self.CQT_MIN_CB_LOG2) * (width >> self.CQT_MIN_CB_LOG2) * hmod.CQT_CELL_DT.itemsize, np.uint8)
+        if finish:          # the decided picture's block structure (havoc.CELL_DT per 4x4 cell) and the loop filter's edge data on the region grid (as d_data / d_bs)
+            regions = ((width + 63) // 64 * 8 + 1) * ((height + 63) // 64 * 8 + 1)
+            self.cqt_block = hv.zeros((height // 4) * (width // 4) * hmod.CELL_DT.itemsize, np.uint8)
+            self.cqt_data, self.cqt_bs = hv.zeros(regions, np.uint8), hv.zeros(regions, np.uint8)     # (data: int8 values)
         # ---- the intra candidates of the picture (an inter picture evaluates them per coding unit): partitions with neighbours from the source
         self.intra_parts = {}
         self.rsl = float(self.params.reciprocal_sqrt_lambda)
@@ -1025,6 +1034,8 @@ class DecisionPicture:
         [H / 8, W / 8]: unit -1 in an undecided CTU))"""
         if not self.commit:
             raise ValueError("cqt_commit_results: the picture was made without commit=True")
+        if self.finish:
+            raise ValueError("cqt_commit_results: with finish=True the committed planes are filtered in place: cqt_finish_results() has them")
         if getattr(self, "_cqt_commit", None) is None:
             hv, pad, c2 = self.hv, self.PAD, self.PAD // 2
             y = hv.down(self.cqt_recon, self.dt)[:self.n].reshape(-1, self.stride)[pad:pad + self.H, pad:pad + self.W]
@@ -1032,6 +1043,33 @@ class DecisionPicture:
             c = np.stack([c[k * self.cpe:k * self.cpe + self.cn].reshape(-1, self.cstride)[c2:c2 + self.H // 2, c2:c2 + self.W // 2] for k in range(2)])
             self._cqt_commit = dict(recon=y.copy(), crecon=c, cells=hv.cqt_cells_download(self.cqt_cells, self.W, self.H, self.CQT_MIN_CB_LOG2))
         return self._cqt_commit
+
+    # ---- the committed picture finished: block structure, boundary strengths, deblocking, padding (turing/TaskDeblock.cpp:105-167) --------------------------------
+    def cqt_finish_launch(self):
+        """behind cqt_commit_launch: the committed cells as 4x4 cells (lists 0 and 1 are two different decoded pictures: dpb indices 0 and 1), the boundary strengths
+        derived from them, deblocking of cqt_recon / cqt_crecon in place, padding of the three planes on all four sides.  Seven launches; asynchronous"""
+        hv, W, H, c2 = self.hv, self.W, self.H, self.PAD // 2
+        o, co, cs = self.origin, self.corigin, self.cstride
+        hv.cqt_block_cells_d(W, H, self.CQT_MIN_CB_LOG2, self.qp, 0, 1, self.cqt_cells, self.cqt_block, W // 4)
+        hv.derive_bs_d(self.cqt_block, W // 4, W, H, self.cqt_data, self.cqt_bs)
+        hv.deblock_d(self.bd, self.cqt_recon, o, self.stride, self.cqt_crecon, co, self.cpe + co, cs, W, H, self.cqt_data, self.cqt_bs)
+        hv.pad_block_d(self.cqt_recon, o, W, H, self.stride, self.PAD)
+        hv.pad_block_d(self.cqt_crecon, co, W // 2, H // 2, cs, c2)
+        hv.pad_block_d(self.cqt_crecon, self.cpe + co, W // 2, H // 2, cs, c2)
+
+    def cqt_finish_results(self):
+        """what cqt_finish_launch() left on the device, as numpy: dict(recon dt [rows, stride]: the whole padded luma plane; crecon dt [2, chroma rows, cstride]: both
+        whole padded chroma planes; cells havoc.CELL_DT [H / 4, W / 4]; data int8, bs uint8: the region grid's edge data)"""
+        if not self.finish:
+            raise ValueError("cqt_finish_results: the picture was made without finish=True")
+        if getattr(self, "_cqt_finish", None) is None:
+            hv = self.hv
+            c = hv.down(self.cqt_crecon, self.dt)
+            self._cqt_finish = dict(recon=hv.down(self.cqt_recon, self.dt)[:self.n].reshape(-1, self.stride).copy(),
+                                    crecon=np.stack([c[k * self.cpe:k * self.cpe + self.cn].reshape(-1, self.cstride) for k in range(2)]),
+                                    cells=hv.down(self.cqt_block, np.uint8).view(self.hmod.CELL_DT).reshape(self.H // 4, self.W // 4).copy(),
+                                    data=hv.down(self.cqt_data, np.int8).copy(), bs=hv.down(self.cqt_bs, np.uint8).copy())
+        return self._cqt_finish
 
     def chroma_chain(self, field):
         """the inter residual of the chroma planes at the decided vectors (turing/Reconstruct.cpp:1274-1286 with cIdx 1, 2): HavocPredUni 4-tap of every unit's
@@ -1700,12 +1738,13 @@ class DecisionPicture:
             # everything after the searches is a FIXED sequence of launches over device-resident tables (the decided field never leaves the device, the decisions
             # between the launches are kernels): recorded once into a HIP graph, one launch per picture, one wait at the end
             self._rqt = self._cells = self._sao_decisions = self._rqt_rates = self._rqt_tree = self._cu_decisions = self._cqt_decisions = None
-            self._unit_tree_decisions = self._cqt_commit = None
+            self._unit_tree_decisions = self._cqt_commit = self._cqt_finish = None
             pu = (self.pu_mode_launches,) if self.pu_modes else ()      # (the tables its launches read went up before the replay: pu_candidates)
             pu += (self.unit_tree_launches,) if self.unit_trees else ()  # (behind pu_decide: it reads the winners in place; before cu_close, which reads its records)
             pu += (self.cu_close_launches,) if self.cu_close else ()     # (after the tree decisions AND the prediction units' rates: it reads both in place)
             pu += (self.cqt_launch,) if self.cqt else ()                 # (behind cu_close: it reads its records in place)
             pu += (self.cqt_commit_launch,) if self.commit else ()       # (directly behind the quadtree: it acts on its records, into buffers of its own)
+            pu += (self.cqt_finish_launch,) if self.finish else ()       # (directly behind the commit: it filters and pads what that wrote, in place)
             if self.sao:
                 self._replayed("after the searches", lambda: (self.merge_candidates(field), self.predict(field), self.sao_filter_inputs(field),
                                                               self.sao_loop_filter(), [f() for f in pu]))

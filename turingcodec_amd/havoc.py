@@ -138,6 +138,7 @@ def _load():
         "unit_pred_select": [_vp, _i, _vp, _vp, _vp, C.c_ssize_t, _vp, C.c_ssize_t, _vp, _vp, _vp, _vp, _i, _vp, _vp],
         "cqt_decide": [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, C.c_size_t, _vp, _vp, _vp, _vp],
         "cqt_commit": [_vp, _vp],
+        "cqt_block_cells": [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _ip],
         "intra_decide_rated": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_int32, _vp, _vp],
         "rqt_decide_rated": [_vp, _vp, _i, _vp, _vp, _vp, _vp, C.c_int64, C.c_ssize_t, _i, _i, _vp],
         "rqt_decide_tree": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_ssize_t, _i, C.c_int64, C.c_int64, C.c_ssize_t, _i, _i, _vp, _vp],
@@ -1163,6 +1164,22 @@ class Havoc:
         """cqt_commit_d's cell map as numpy: CQT_CELL_DT [height >> min_cb_log2, width >> min_cb_log2]"""
         hc, wc = height >> min_cb_log2, width >> min_cb_log2
         return self.down(cells, np.uint8)[:hc * wc * CQT_CELL_DT.itemsize].view(CQT_CELL_DT).reshape(hc, wc).copy()
+
+    def cqt_block_cells_d(self, width, height, min_cb_log2, qp, dpb0, dpb1, cqt_cells, cells, cells_stride):
+        """cqt_commit_d's cell map as the (height / 4) x (width / 4) map of CELL_DT records derive_bs_d reads, rows cells_stride cells apart, every cell written
+        (havoc_mi355x_cqt_block_cells); cqt_cells, cells: uint8 tensors.  No sync."""
+        self._ck(self.L.havoc_mi355x_cqt_block_cells(self.h, int(width), int(height), int(min_cb_log2), int(qp), int(dpb0), int(dpb1), _ptr(cqt_cells), _ptr(cells),
+                                                     int(cells_stride)))
+
+    def cqt_block_cells(self, cqt_cells, width, height, min_cb_log2, qp, dpb0, dpb1):
+        """numpy level: cqt_cells CQT_CELL_DT [height >> min_cb_log2, width >> min_cb_log2] -> CELL_DT [height / 4, width / 4]"""
+        import torch
+        cqt_cells = np.ascontiguousarray(cqt_cells, CQT_CELL_DT)
+        with torch.cuda.stream(self.tstream):
+            d_cqt = torch.from_numpy(cqt_cells.view(np.uint8).reshape(-1).copy()).to(self.device)
+            d_cells = torch.zeros((height // 4) * (width // 4) * CELL_DT.itemsize, dtype=torch.uint8, device=self.device)
+        self.cqt_block_cells_d(width, height, min_cb_log2, qp, dpb0, dpb1, d_cqt, d_cells, width // 4)
+        return self.down(d_cells, np.uint8).view(CELL_DT).reshape(height // 4, width // 4).copy()
 
     def unit_pred_ssd_d(self, bit_depth, src_y, src_stride, src_c, src_stride_c, pred_y, pred_stride, pred_c, pred_stride_c, jobs, out):
         """SSD(source, prediction) of units' luma, Cb and Cr blocks in one launch (havoc_mi355x_unit_pred_ssd); jobs: uint8 tensor of PRED_SSD_JOB_DT; out: int32 [3 n].

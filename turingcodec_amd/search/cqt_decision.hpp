@@ -329,4 +329,42 @@ inline int commitCqt(const CqtCommit<Sample> &P, int ctu, bool decided, const in
     return done;
 }
 
+// ---- the committed cells as the loop filter's block structure: the map of 4x4 cells havoc_mi355x_derive_bs reads, every coding unit one inter 2Nx2N prediction unit.
+// havoc_mi355x_cqt_block_cells does this in one launch, byte for byte; this is its host form, data-only.  What LoopFilter::Picture::processCu / processPu / processTu /
+// processRc see of the decided picture (turing/LoopFilter.h:541-737).
+struct CqtBlockCell         // = havoc_mi355x_cell, 16 bytes
+{
+    int16_t mv[2][2];
+    int8_t dpbIndex[2];
+    uint8_t flags;
+    int8_t qpY;
+    uint8_t tuLog2;
+    uint8_t reserved[3];
+};
+constexpr int kCellCoded = 2, kCellNoFilter = 4, kCellPuLeft = 8, kCellPuTop = 16;      // HAVOC_CELL_*
+
+// cqt: (height >> minCbLog2) rows of (width >> minCbLog2) committed cells; cells: (height / 4) rows of (width / 4), `stride` cells apart, every one written.  A coding
+// unit is aligned to its size, so a cell's own position names its unit's origin.
+inline void cqtBlockCells(int width, int height, int minCbLog2, int qp, int dpb0, int dpb1, const CqtCommitCell *cqt, CqtBlockCell *cells, long stride)
+{
+    const int wc = width >> minCbLog2;
+    for (int y = 0; y < height; y += 4)
+        for (int x = 0; x < width; x += 4)
+        {
+            const CqtCommitCell &q = cqt[long(y >> minCbLog2) * wc + (x >> minCbLog2)];
+            CqtBlockCell c = {{{0, 0}, {0, 0}}, {-1, -1}, uint8_t(kCellNoFilter), int8_t(qp), 2, {0, 0, 0}};     // an undecided CTU's: nobody's samples, left alone
+            if (q.unit >= 0)
+            {
+                const int size = 1 << q.log2Size, ox = x & (size - 1), oy = y & (size - 1);
+                const int k = q.trDepth ? (oy >= size / 2) * 2 + (ox >= size / 2) : 0;
+                for (int l = 0; l < 2; ++l) c.mv[l][0] = q.mv[l][0], c.mv[l][1] = q.mv[l][1];
+                c.dpbIndex[0] = int8_t(q.pred != 1 ? dpb0 : -1);
+                c.dpbIndex[1] = int8_t(q.pred != 0 ? dpb1 : -1);
+                c.flags = uint8_t((q.outcome == 0 && (q.cbf >> k & 1) ? kCellCoded : 0) | (ox == 0 ? kCellPuLeft : 0) | (oy == 0 ? kCellPuTop : 0));
+                c.tuLog2 = uint8_t(q.log2Size - q.trDepth < 5 ? q.log2Size - q.trDepth : 5);
+            }
+            cells[long(y >> 2) * stride + (x >> 2)] = c;
+        }
+}
+
 } // namespace havoc_search
