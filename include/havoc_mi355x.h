@@ -1256,6 +1256,71 @@ int havoc_mi355x_cqt_commit(havoc_mi355x_ctx *ctx, const havoc_mi355x_cqt_commit
 int havoc_mi355x_cqt_block_cells(havoc_mi355x_ctx *ctx, int width, int height, int min_cb_log2, int qp, int dpb_index0, int dpb_index1,
                                  const havoc_mi355x_cqt_cell *d_cqt_cells, havoc_mi355x_cell *d_cells, intptr_t cells_stride);
 
+/* ---- the committed cells as the collocated motion store (csrc/kernels_cqt.hip: k_cqt_motion_store) ----
+ * The other half of a reference picture: beside the deblocked, padded planes (TaskDeblock.cpp:105-167) the motion the NEXT picture's temporal candidate is derived
+ * from (turing/StateCollocatedMotion.h:51-122).  The store is (height + 15) / 16 dense rows of (width + 15) / 16 records -- StateCollocatedMotion's own dimensions --
+ * and entry (X, Y) holds the motion of the coding unit that CONTAINS luma sample (16 X, 16 Y): fillRectangle (:75-90) writes every X, Y with x0 <= 16 X < x1 and
+ * y0 <= 16 Y < y1, so an 8x8 unit whose origin is no multiple of 16 writes no entry, a 64x64 unit writes sixteen, and -- the final units partition a decided CTU --
+ * every entry has one writer.  The sample is inside the picture (width and height are multiples of MinCb, 16 X < width, 16 Y < height).
+ * Entry (X, Y) reads q = d_cqt_cells[(16 Y >> min_cb_log2) * (width >> min_cb_log2) + (16 X >> min_cb_log2)]:
+ *   - q.unit < 0 (an undecided CTU: all-ones bytes): the whole record is zero ("not available", the reference's default PuData; an intra unit would look the same);
+ *     no other field of q is read;
+ *   - otherwise pred_flag[0] = q.pred != 1, pred_flag[1] = q.pred != 0; for a used list mv[l] = q.mv[l] and ref_poc[l] = ref_poc0 / ref_poc1, for an unused list
+ *     both are 0; long_term = 0, reserved = 0.  cand, outcome, tr_depth, cbf and log2_size are not read.
+ * Argument order: ctx, width, height, min_cb_log2, poc (the committed picture's own picture order count), ref_poc0, ref_poc1 (of the pictures behind lists 0 and 1,
+ * reference index 0), d_cqt_cells (in), d_store (out).
+ * The input is trusted and never written.  EINVAL: a null pointer; min_cb_log2 outside 3..6; a width or height that is not a positive multiple of 1 << min_cb_log2;
+ * ref_poc0 == poc or ref_poc1 == poc (a picture does not predict from itself: the derivation would divide by zero); poc - ref_poc0 or poc - ref_poc1 outside
+ * -32768..32767 (DiffPicOrderCnt); d_store == d_cqt_cells; either pointer not 8-byte aligned.
+ * One launch; no allocation, no synchronisation, no workspace: capturable into a HIP graph. */
+typedef struct {
+    int16_t mv[2][2];       /* [list][x, y], quarter samples; a list without motion: 0, 0 */
+    int32_t ref_poc[2];     /* picture order count of the picture the list's vector points into; 0 without motion */
+    uint8_t pred_flag[2];   /* neither: not available (intra, or not coded) */
+    uint8_t long_term[2];
+    uint32_t reserved;      /* 0 */
+} havoc_mi355x_col_cell;    /* sizeof: 24; = ColocatedCell of turingcodec_amd/search/amvp.hpp as plain data */
+int havoc_mi355x_cqt_motion_store(havoc_mi355x_ctx *ctx, int width, int height, int min_cb_log2, int poc, int ref_poc0, int ref_poc1,
+                                  const havoc_mi355x_cqt_cell *d_cqt_cells, havoc_mi355x_col_cell *d_store);
+
+/* ---- the temporal motion vector candidate of a picture's prediction units (csrc/kernels_temporal.hip: k_temporal_candidates) ----
+ * What AMVP (turing/Mvp.h:195-436) and the merge list (:486-716) start from: per prediction unit and list, the candidate derived from the collocated picture's motion
+ * store (Mvp.h:44-181; HEVC 8.5.3.2.8 / 8.5.3.2.9).  The rule is deriveTemporalCandidate of turingcodec_amd/search/amvp.hpp -- pinned against the traced reference
+ * encoder -- compiled into the kernel as it stands.
+ * d_store: havoc_mi355x_col_cell records, rows store_stride records apart, (pic_height + 15) / 16 rows of (pic_width + 15) / 16.  d_pus: havoc_picture_pu[n]
+ * (turingcodec_amd/search/search_abi.h; x0, y0, w, h are read, nothing else).  d_out[2 * pu + list], like the search results.
+ * For the unit (x0, y0, w, h) and list X towards target_poc[X]:
+ *   - the bottom-right cell ((x0 + w) >> 4, (y0 + h) >> 4) is consulted only when (y0 >> ctb_log2) == ((y0 + h) >> ctb_log2), y0 + h < pic_height and
+ *     x0 + w < pic_width; else, or when it gives nothing, the centre cell ((x0 + w / 2) >> 4, (y0 + h / 2) >> 4).  No cell outside the store is ever read;
+ *   - a cell gives nothing when neither pred_flag is set, or its chosen list is long-term, or -- THIS PROJECT'S OWN RULE -- its chosen list has ref_poc == col_poc
+ *     (the reference would divide by zero; no conforming stream has the case).  The chosen list: the only one set; with both, list X when all_backwards, else list 1
+ *     when collocated_from_l0, else list 0;
+ *   - the vector is taken as it is when col_poc - ref_poc == cur_poc - target_poc[X], else scaled by the two distances (8.5.3.2.7: both clipped to -128..127, the
+ *     factor to -4096..4095, the components to -32768..32767);
+ *   - a unit that is not inside the picture (x0 < 0, y0 < 0, w <= 0, h <= 0, x0 + w > pic_width or y0 + h > pic_height) has no candidate.
+ * A candidate that is not available has mv 0, 0 and source 0.
+ * Argument order: ctx, params, d_store (in), store_stride, d_pus (in), n, d_out (out).
+ * The inputs are trusted and never written.  EINVAL: a null pointer; n < 0; ctb_log2 outside 4..6; a pic_width or pic_height that is not positive;
+ * store_stride < (pic_width + 15) / 16; target_poc[l] == cur_poc; all_backwards or collocated_from_l0 outside 0 / 1; a non-zero reserved word; d_store, d_pus or
+ * d_out not 8-byte aligned; d_out == d_store or d_out == d_pus.  n == 0: returns 0 without a launch.
+ * One launch; no allocation, no synchronisation, no workspace: capturable into a HIP graph. */
+typedef struct {
+    int32_t pic_width, pic_height, ctb_log2;
+    int32_t col_poc;                /* picture order count of the collocated picture (the store's) */
+    int32_t cur_poc;                /* ... of the picture the prediction units belong to */
+    int32_t target_poc[2];          /* ... of RefPicList0[0] / RefPicList1[0] of that picture */
+    int32_t all_backwards;          /* 0 / 1: every reference picture of the current picture precedes it in output order */
+    int32_t collocated_from_l0;     /* 0 / 1: collocated_from_l0_flag */
+    int32_t reserved[3];            /* 0 */
+} havoc_mi355x_temporal_params;     /* sizeof: 48 */
+typedef struct {
+    int16_t mv[2];          /* x, y in quarter samples; 0, 0 when not available */
+    int16_t available;      /* 0 / 1 */
+    int16_t source;         /* 0 none, 1 the bottom-right cell, 2 the centre cell */
+} havoc_mi355x_temporal_cand;       /* sizeof: 8 */
+int havoc_mi355x_temporal_candidates(havoc_mi355x_ctx *ctx, const havoc_mi355x_temporal_params *params, const havoc_mi355x_col_cell *d_store, intptr_t store_stride,
+                                     const void *d_pus, int n, havoc_mi355x_temporal_cand *d_out);
+
 /* ---- an intra picture's partitions with their real dependencies (round 4; csrc/kernels_decide.hip) ----
  * A partition predicts from the reconstruction of what precedes it (turing/Reconstruct.cpp:609-615) and takes candModeList from its neighbours' decided modes
  * (turing/CandModeList.h:33-95).  A client that runs the batch chain over the partitions level by level (every partition of a level has all its neighbours final)

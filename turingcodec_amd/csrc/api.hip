@@ -1287,4 +1287,45 @@ int havoc_mi355x_cqt_block_cells(havoc_mi355x_ctx *ctx, int width, int height, i
     return check(launch_cqt_block_cells(LS(ctx), width, height, min_cb_log2, qp, dpb_index0, dpb_index1, d_cqt_cells, d_cells, cells_stride), "cqt_block_cells");
 }
 
+int havoc_mi355x_cqt_motion_store(havoc_mi355x_ctx *ctx, int width, int height, int min_cb_log2, int poc, int ref_poc0, int ref_poc1,
+                                  const havoc_mi355x_cqt_cell *d_cqt_cells, havoc_mi355x_col_cell *d_store)
+{
+    REQUIRE_CTX();
+    REQUIRE(d_cqt_cells != nullptr && d_store != nullptr, "cqt_motion_store: null device pointer");
+    REQUIRE(min_cb_log2 >= 3 && min_cb_log2 <= 6, "cqt_motion_store: min_cb_log2 must be 3..6");
+    REQUIRE(width > 0 && height > 0 && width % (1 << min_cb_log2) == 0 && height % (1 << min_cb_log2) == 0,
+            "cqt_motion_store: width and height must be positive multiples of the minimum coding block size");
+    REQUIRE(ref_poc0 != poc && ref_poc1 != poc, "cqt_motion_store: a ref_poc equal to poc (a picture does not predict from itself)");
+    for (long long d : {(long long)poc - ref_poc0, (long long)poc - ref_poc1})
+        REQUIRE(d >= -32768 && d <= 32767, "cqt_motion_store: a poc difference outside -32768..32767");
+    REQUIRE(static_cast<const void *>(d_store) != static_cast<const void *>(d_cqt_cells), "cqt_motion_store: the destination must not be the input (which is never written)");
+    REQUIRE((reinterpret_cast<uintptr_t>(d_cqt_cells) & 7) == 0 && (reinterpret_cast<uintptr_t>(d_store) & 7) == 0,
+            "cqt_motion_store: d_cqt_cells and d_store must be 8-byte aligned");
+    REQUIRE((long long)((width + 15) >> 4) * ((height + 15) >> 4) < (1ll << 31) - 256, "cqt_motion_store: too many entries");
+    return check(launch_cqt_motion_store(LS(ctx), width, height, min_cb_log2, ref_poc0, ref_poc1, d_cqt_cells, d_store), "cqt_motion_store");
+}
+
+int havoc_mi355x_temporal_candidates(havoc_mi355x_ctx *ctx, const havoc_mi355x_temporal_params *params, const havoc_mi355x_col_cell *d_store, intptr_t store_stride,
+                                     const void *d_pus, int n, havoc_mi355x_temporal_cand *d_out)
+{
+    REQUIRE_CTX();
+    REQUIRE(params != nullptr, "temporal_candidates: null params");
+    REQUIRE(d_store != nullptr && d_pus != nullptr && d_out != nullptr, "temporal_candidates: null device pointer");
+    REQUIRE(n >= 0 && n < (1 << 30), "temporal_candidates: n must be 0 .. 2^30 - 1");
+    REQUIRE(params->ctb_log2 >= 4 && params->ctb_log2 <= 6, "temporal_candidates: ctb_log2 must be 4..6");
+    REQUIRE(params->pic_width > 0 && params->pic_height > 0, "temporal_candidates: pic_width and pic_height must be positive");
+    REQUIRE(store_stride >= ((intptr_t)params->pic_width + 15) / 16, "temporal_candidates: store_stride must be at least (pic_width + 15) / 16");
+    REQUIRE(params->target_poc[0] != params->cur_poc && params->target_poc[1] != params->cur_poc,
+            "temporal_candidates: a target_poc equal to cur_poc (a picture does not predict from itself)");
+    REQUIRE((params->all_backwards == 0 || params->all_backwards == 1) && (params->collocated_from_l0 == 0 || params->collocated_from_l0 == 1),
+            "temporal_candidates: all_backwards and collocated_from_l0 are flags: 0 or 1");
+    REQUIRE(params->reserved[0] == 0 && params->reserved[1] == 0 && params->reserved[2] == 0, "temporal_candidates: reserved words must be 0");
+    REQUIRE((reinterpret_cast<uintptr_t>(d_store) & 7) == 0 && (reinterpret_cast<uintptr_t>(d_pus) & 7) == 0 && (reinterpret_cast<uintptr_t>(d_out) & 7) == 0,
+            "temporal_candidates: d_store, d_pus and d_out must be 8-byte aligned");
+    REQUIRE(static_cast<const void *>(d_out) != static_cast<const void *>(d_store) && static_cast<const void *>(d_out) != d_pus,
+            "temporal_candidates: the destination must not be an input (which is never written)");
+    if (n == 0) return 0;
+    return check(launch_temporal_candidates(LS(ctx), *params, d_store, (long)store_stride, d_pus, n, d_out), "temporal_candidates");
+}
+
 } // extern "C"

@@ -18,6 +18,7 @@
 // A wait that gives up raises the give-up word; the rows below are let through and k_cqt_finish clears `decided` in every record of the call.
 // k_cqt_commit (below, with its own comment) acts on the decision: the final units of every decided CTU into one picture and a per-cell field.  DESIGN 7, row f2^8.
 // k_cqt_block_cells (below) turns that field into the 4x4 cells the loop filter's boundary strengths are derived from.  DESIGN 7, row f2^9.
+// k_cqt_motion_store (below) turns it into the collocated motion store the next picture's temporal candidate is derived from.  DESIGN 7, row f2^10.
 #include "cabac_tables.h"
 #include "common.h"
 #include "launch.h"
@@ -531,6 +532,28 @@ __global__ __launch_bounds__(256) void k_cqt_block_cells(const havoc_mi355x_cqt_
     *reinterpret_cast<u32x4 *>(cells + (long)cy * stride + cx) = u32x4{(unsigned int)v, (unsigned int)(v >> 32), d0 | d1 << 8 | flags << 16 | (unsigned int)qp << 24, tu};
 }
 
+// k_cqt_motion_store: the collocated motion store of the committed picture, one 24-byte record per 16x16 luma samples (DESIGN 7, row f2^10; the rule is stated in
+// include/havoc_mi355x.h and restated in search/cqt_decision.hpp: cqtMotionStore).  A lane per ENTRY in raster order: three aligned 8-byte loads of the committed cell
+// that covers luma sample (16 X, 16 Y) -- the one unit whose fillRectangle writes the entry --, every branch a select, three aligned 8-byte stores.  8 160 entries at
+// 1080p: the launch is bound by its latency, nothing cleverer is wanted.
+__global__ __launch_bounds__(256) void k_cqt_motion_store(const havoc_mi355x_cqt_cell *__restrict__ q, int sw, int count, int minCbLog2, int qcw, int refPoc0, int refPoc1,
+                                                          havoc_mi355x_col_cell *__restrict__ store)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    const int Y = i / sw, X = i - Y * sw;
+    const unsigned long long *r = reinterpret_cast<const unsigned long long *>(q + (long)((Y << 4) >> minCbLog2) * qcw + ((X << 4) >> minCbLog2));
+    const unsigned long long head = r[0], mv = r[1], tail = r[2];
+    const bool decided = (int)(unsigned int)head >= 0;          // unit -1: the commit left all-ones bytes, nothing else of the record means anything
+    const int pred = (unsigned int)tail >> 16 & 255;
+    const bool p0 = decided && pred != 1, p1 = decided && pred != 0;
+    const unsigned long long use = (p0 ? 0xffffffffull : 0ull) | (p1 ? 0xffffffff00000000ull : 0ull);
+    unsigned long long *o = reinterpret_cast<unsigned long long *>(store + i);
+    o[0] = mv & use;
+    o[1] = ((unsigned long long)(unsigned int)refPoc0 | (unsigned long long)(unsigned int)refPoc1 << 32) & use;
+    o[2] = (p0 ? 1ull : 0ull) | (p1 ? 256ull : 0ull);          // pred_flag[0], pred_flag[1]; long_term 0, 0; reserved 0
+}
+
 } // namespace
 
 hipError_t launch_cqt_commit(hipStream_t st, const havoc_mi355x_cqt_commit_args &A)
@@ -554,6 +577,14 @@ hipError_t launch_cqt_block_cells(hipStream_t st, int width, int height, int min
     const int cw = width >> 2, count = cw * (height >> 2);
     hipLaunchKernelGGL(k_cqt_block_cells, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, cqtCells, cw, count, minCbLog2, width >> minCbLog2, qp, dpb0, dpb1, cells,
                        stride);
+    return hipGetLastError();
+}
+
+hipError_t launch_cqt_motion_store(hipStream_t st, int width, int height, int minCbLog2, int refPoc0, int refPoc1, const havoc_mi355x_cqt_cell *cqtCells,
+                                   havoc_mi355x_col_cell *store)
+{
+    const int sw = (width + 15) >> 4, count = sw * ((height + 15) >> 4);
+    hipLaunchKernelGGL(k_cqt_motion_store, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, cqtCells, sw, count, minCbLog2, width >> minCbLog2, refPoc0, refPoc1, store);
     return hipGetLastError();
 }
 

@@ -64,6 +64,9 @@ hipError_t launch_cqt_decide(hipStream_t, int width, int height, int ctbLog2, in
 hipError_t launch_cqt_commit(hipStream_t, const havoc_mi355x_cqt_commit_args &);
 hipError_t launch_cqt_block_cells(hipStream_t, int width, int height, int minCbLog2, int qp, int dpb0, int dpb1, const havoc_mi355x_cqt_cell *, havoc_mi355x_cell *,
                                   long stride);
+hipError_t launch_cqt_motion_store(hipStream_t, int width, int height, int minCbLog2, int refPoc0, int refPoc1, const havoc_mi355x_cqt_cell *, havoc_mi355x_col_cell *);
+hipError_t launch_temporal_candidates(hipStream_t, const havoc_mi355x_temporal_params &, const havoc_mi355x_col_cell *, long stride, const void *pus, int n,
+                                      havoc_mi355x_temporal_cand *);
 hipError_t launch_intra_order(hipStream_t, const int32_t *, const havoc_mi355x_intra_mpm *, int, int32_t, int32_t *, int32_t *, int32_t *, int32_t *);
 hipError_t launch_intra_expand(hipStream_t, const havoc_mi355x_intra_search_job *, const int32_t *, const int32_t *, const int32_t *, const int32_t *, int, int, int, int, int,
                                int, int, int, havoc_mi355x_intra_job *, havoc_mi355x_tu_fused_job *, havoc_mi355x_rdoq_job *, int32_t *, int32_t *);

@@ -462,8 +462,21 @@ class DecisionPicture:
     PAD = 96
 
     def __init__(self, hv, width, height, bit_depth=8, qp=32, seed=11, threads=16, frames=None, density=1.0, intra=True, search_on_device=True, distance=1,
-                 sao=False, residual_rates=False, tree_rates=False, pu_modes=False, cu_close=False, cqt=False, unit_trees=False, commit=False, finish=False):
+                 sao=False, residual_rates=False, tree_rates=False, pu_modes=False, cu_close=False, cqt=False, unit_trees=False, commit=False, finish=False,
+                 motion=None, col=None):
+        """motion=(poc, ref_poc0, ref_poc1) (needs commit=True): the committed picture also leaves its collocated motion store in `cqt_store`
+        (havoc_mi355x_cqt_motion_store, directly behind the commit inside the replayed graph; cqt_motion_results()) -- with finish=True the two things a reference
+        picture is.
+        col=dict(store=<device tensor of havoc.COL_CELL_DT records, dense rows: another picture's cqt_store>, col_poc=, cur_poc=, target_poc=(l0, l1), all_backwards=,
+        collocated_from_l0=) (device search route only): the temporal candidate of every unit of self.pus per list from that store
+        (havoc_mi355x_temporal_candidates, inside the replayed graph; temporal_candidates()).  The store belongs to ANOTHER picture: that the step which writes it
+        has finished (or is ordered before this picture's step on the same stream) is the caller's to establish, and the tensor must stay alive and in place --
+        the recorded graph holds its address.  The candidates are produced, not yet consumed: the search walk's predictors do not read them."""
         import torch
+        if motion is not None and not commit:
+            raise ValueError("motion=(poc, ref_poc0, ref_poc1) makes the collocated motion store of the committed picture: it needs commit=True")
+        if col is not None and not search_on_device:
+            raise ValueError("col= needs the device route (search_on_device=True)")
         if finish and not commit:
             raise ValueError("finish=True deblocks and pads the committed picture: it needs commit=True")
         if commit and not (unit_trees and cqt):
@@ -517,7 +530,11 @@ class DecisionPicture:
         # ... and finished as TaskDeblock.cpp:105-167 finishes a picture before it is used for prediction: the committed cells as 4x4 cells (havoc_mi355x_cqt_block_cells),
         # boundary strengths, deblocking of cqt_recon / cqt_crecon in place, padding of the three planes
         self.finish = finish
-        self.sao = sao                                # in-loop SAO between deblocking and padding (sao_filter_inputs / sao_loop_filter)
+        # ... and its motion as the store the next picture's temporal candidate is derived from (havoc_mi355x_cqt_motion_store): (poc, ref_poc0, ref_poc1) or None
+        self.motion = None if motion is None else tuple(int(v) for v in motion)
+        # this picture's own temporal candidates from ANOTHER picture's store (havoc_mi355x_temporal_candidates): the caller's dict or None
+        self.col = None if col is None else dict(col)
+        self.sao = sao                               # in-loop SAO between deblocking and padding (sao_filter_inputs / sao_loop_filter)
         from . import havoc as hmod
         from . import workload
         self.hv, self.torch, self.hmod = hv, torch, hmod
@@ -613,6 +630,19 @@ class DecisionPicture:
             regions = ((width + 63) // 64 * 8 + 1) * ((height + 63) // 64 * 8 + 1)
             self.cqt_block = hv.zeros((height // 4) * (width // 4) * hmod.CELL_DT.itemsize, np.uint8)
             self.cqt_data, self.cqt_bs = hv.zeros(regions, np.uint8), hv.zeros(regions, np.uint8)     # (data: int8 values)
+        if self.motion is not None:     # the decided picture's collocated motion store: havoc.COL_CELL_DT per 16x16 luma samples, dense rows
+            if len(self.motion) != 3:
+                raise ValueError("motion must be (poc, ref_poc0, ref_poc1)")
+            self.cqt_store = hv.zeros(((height + 15) // 16) * ((width + 15) // 16) * hmod.COL_CELL_DT.itemsize, np.uint8)
+        if self.col is not None:        # the units' table on the device (as the search's own copy of it is laid out) and a record per (unit, list)
+            missing = {"store", "col_poc", "cur_poc", "target_poc", "all_backwards", "collocated_from_l0"} ^ set(self.col)
+            if missing:
+                raise ValueError("col= takes exactly store, col_poc, cur_poc, target_poc, all_backwards, collocated_from_l0: %s" % sorted(missing))
+            c = self.col
+            self._temporal_params = hmod.temporal_params(width, height, self.CQT_CTB_LOG2, c["col_poc"], c["cur_poc"], c["target_poc"], c["all_backwards"],
+                                                         c["collocated_from_l0"])
+            self._d_temporal_pus = hv.up(np.ascontiguousarray(self.pus).view(np.uint8).reshape(-1))
+            self._d_temporal = hv.zeros(max(1, 2 * len(self.pus)) * hmod.TEMPORAL_CAND_DT.itemsize, np.uint8)
         # ---- the intra candidates of the picture (an inter picture evaluates them per coding unit): partitions with neighbours from the source
         self.intra_parts = {}
         self.rsl = float(self.params.reciprocal_sqrt_lambda)
@@ -1043,6 +1073,36 @@ class DecisionPicture:
             c = np.stack([c[k * self.cpe:k * self.cpe + self.cn].reshape(-1, self.cstride)[c2:c2 + self.H // 2, c2:c2 + self.W // 2] for k in range(2)])
             self._cqt_commit = dict(recon=y.copy(), crecon=c, cells=hv.cqt_cells_download(self.cqt_cells, self.W, self.H, self.CQT_MIN_CB_LOG2))
         return self._cqt_commit
+
+    # ---- the committed picture's motion as the next picture's collocated store (turing/StateCollocatedMotion.h:51-122) -------------------------------------------
+    def cqt_motion_launch(self):
+        """directly behind cqt_commit_launch: cqt_cells as the collocated motion store, into cqt_store.  It reads cqt_cells only -- with or without finish.  One
+        launch; asynchronous"""
+        poc, ref_poc0, ref_poc1 = self.motion
+        self.hv.cqt_motion_store_d(self.W, self.H, self.CQT_MIN_CB_LOG2, poc, ref_poc0, ref_poc1, self.cqt_cells, self.cqt_store)
+
+    def cqt_motion_results(self):
+        """what cqt_motion_launch() left on the device, as numpy: havoc.COL_CELL_DT [(H + 15) // 16, (W + 15) // 16]"""
+        if self.motion is None:
+            raise ValueError("cqt_motion_results: the picture was made without motion=(poc, ref_poc0, ref_poc1)")
+        if getattr(self, "_cqt_motion", None) is None:
+            self._cqt_motion = self.hv.down(self.cqt_store, np.uint8).view(self.hmod.COL_CELL_DT).reshape((self.H + 15) // 16, (self.W + 15) // 16).copy()
+        return self._cqt_motion
+
+    # ---- this picture's temporal candidates from another picture's store (turing/Mvp.h:44-181) --------------------------------------------------------------------
+    def temporal_launch(self):
+        """the temporal candidate of every unit of self.pus, per list, from col["store"] (dense rows).  It reads nothing this picture's step writes.  One launch;
+        asynchronous.  Ordering against the step that writes the store is the caller's (see __init__)"""
+        self.hv.temporal_candidates_d(self._temporal_params, self.col["store"], (self.W + 15) // 16, self._d_temporal_pus, len(self.pus), self._d_temporal)
+
+    def temporal_candidates(self):
+        """what temporal_launch() left on the device, as numpy: havoc.TEMPORAL_CAND_DT [len(self.pus), 2] (unit, list)"""
+        if self.col is None:
+            raise ValueError("temporal_candidates: the picture was made without col=")
+        if getattr(self, "_temporal", None) is None:
+            n = len(self.pus)
+            self._temporal = self.hv.down(self._d_temporal, np.uint8)[:2 * n * self.hmod.TEMPORAL_CAND_DT.itemsize].view(self.hmod.TEMPORAL_CAND_DT).reshape(n, 2).copy()
+        return self._temporal
 
     # ---- the committed picture finished: block structure, boundary strengths, deblocking, padding (turing/TaskDeblock.cpp:105-167) --------------------------------
     def cqt_finish_launch(self):
@@ -1738,13 +1798,15 @@ class DecisionPicture:
             # everything after the searches is a FIXED sequence of launches over device-resident tables (the decided field never leaves the device, the decisions
             # between the launches are kernels): recorded once into a HIP graph, one launch per picture, one wait at the end
             self._rqt = self._cells = self._sao_decisions = self._rqt_rates = self._rqt_tree = self._cu_decisions = self._cqt_decisions = None
-            self._unit_tree_decisions = self._cqt_commit = self._cqt_finish = None
+            self._unit_tree_decisions = self._cqt_commit = self._cqt_finish = self._cqt_motion = self._temporal = None
             pu = (self.pu_mode_launches,) if self.pu_modes else ()      # (the tables its launches read went up before the replay: pu_candidates)
             pu += (self.unit_tree_launches,) if self.unit_trees else ()  # (behind pu_decide: it reads the winners in place; before cu_close, which reads its records)
             pu += (self.cu_close_launches,) if self.cu_close else ()     # (after the tree decisions AND the prediction units' rates: it reads both in place)
             pu += (self.cqt_launch,) if self.cqt else ()                 # (behind cu_close: it reads its records in place)
             pu += (self.cqt_commit_launch,) if self.commit else ()       # (directly behind the quadtree: it acts on its records, into buffers of its own)
-            pu += (self.cqt_finish_launch,) if self.finish else ()       # (directly behind the commit: it filters and pads what that wrote, in place)
+            pu += (self.cqt_motion_launch,) if self.motion is not None else ()      # (directly behind the commit: it reads the cells that wrote, nothing else)
+            pu += (self.cqt_finish_launch,) if self.finish else ()       # (behind the commit: it filters and pads what that wrote, in place)
+            pu += (self.temporal_launch,) if self.col is not None else ()           # (reads another picture's store and this picture's unit table only)
             if self.sao:
                 self._replayed("after the searches", lambda: (self.merge_candidates(field), self.predict(field), self.sao_filter_inputs(field),
                                                               self.sao_loop_filter(), [f() for f in pu]))
@@ -1820,6 +1882,8 @@ class DecisionPicture:
             raise ValueError("step_banded does not decide coding quadtrees: use step() with cqt=True")
         if self.unit_trees:
             raise ValueError("step_banded does not build the searched units' trees: use step() with unit_trees=True")
+        if self.col is not None:
+            raise ValueError("step_banded does not derive temporal candidates: use step() with col=")
         if self.sao:
             # SAO of band b reads the deblocked rows of band b + 1 (turing/TaskSao.cpp:46-56): not built
             raise ValueError("step_banded does not run SAO: use step() with sao=True")

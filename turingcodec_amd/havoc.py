@@ -139,6 +139,8 @@ def _load():
         "cqt_decide": [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, C.c_size_t, _vp, _vp, _vp, _vp],
         "cqt_commit": [_vp, _vp],
         "cqt_block_cells": [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _ip],
+        "cqt_motion_store": [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
+        "temporal_candidates": [_vp, _vp, _vp, _ip, _vp, _i, _vp],
         "intra_decide_rated": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_int32, _vp, _vp],
         "rqt_decide_rated": [_vp, _vp, _i, _vp, _vp, _vp, _vp, C.c_int64, C.c_ssize_t, _i, _i, _vp],
         "rqt_decide_tree": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_ssize_t, _i, C.c_int64, C.c_int64, C.c_ssize_t, _i, _i, _vp, _vp],
@@ -365,6 +367,22 @@ CQT_NODE_FINAL, CQT_NODE_FLAG_CODED, CQT_NODE_MUST_SPLIT, CQT_NODE_ECU_STOP, CQT
 # one havoc_mi355x_cqt_cell (include/havoc_mi355x.h), 24 bytes: the decided coding unit that covers a MinCb cell; all-ones bytes (unit -1): none
 CQT_CELL_DT = np.dtype([("unit", "<i4"), ("cand", "<i4"), ("mv", "<i2", (2, 2)), ("log2_size", "u1"), ("outcome", "u1"), ("pred", "u1"), ("tr_depth", "u1"), ("cbf", "<u4")])
 assert CQT_CELL_DT.itemsize == 24
+# one havoc_mi355x_col_cell, 24 bytes: an entry of the collocated motion store (one per 16x16 luma samples); one havoc_mi355x_temporal_params, 48 bytes; one
+# havoc_mi355x_temporal_cand, 8 bytes: a prediction unit's temporal candidate for one list (source: 0 none, 1 the bottom-right cell, 2 the centre cell)
+COL_CELL_DT = np.dtype([("mv", "<i2", (2, 2)), ("ref_poc", "<i4", (2,)), ("pred_flag", "u1", (2,)), ("long_term", "u1", (2,)), ("reserved", "<u4")])
+TEMPORAL_PARAMS_DT = np.dtype([("pic_width", "<i4"), ("pic_height", "<i4"), ("ctb_log2", "<i4"), ("col_poc", "<i4"), ("cur_poc", "<i4"), ("target_poc", "<i4", (2,)),
+                               ("all_backwards", "<i4"), ("collocated_from_l0", "<i4"), ("reserved", "<i4", (3,))])
+TEMPORAL_CAND_DT = np.dtype([("mv", "<i2", (2,)), ("available", "<i2"), ("source", "<i2")])
+assert COL_CELL_DT.itemsize == 24 and TEMPORAL_PARAMS_DT.itemsize == 48 and TEMPORAL_CAND_DT.itemsize == 8
+TEMPORAL_NONE, TEMPORAL_BOTTOM_RIGHT, TEMPORAL_CENTRE = 0, 1, 2
+
+
+def temporal_params(pic_width, pic_height, ctb_log2, col_poc, cur_poc, target_poc, all_backwards, collocated_from_l0):
+    """-> one TEMPORAL_PARAMS_DT record"""
+    p = np.zeros(1, TEMPORAL_PARAMS_DT)
+    p["pic_width"], p["pic_height"], p["ctb_log2"], p["col_poc"], p["cur_poc"] = pic_width, pic_height, ctb_log2, col_poc, cur_poc
+    p["target_poc"], p["all_backwards"], p["collocated_from_l0"] = tuple(target_poc), int(all_backwards), int(collocated_from_l0)
+    return p
 
 
 class CqtCommitArgs(C.Structure):
@@ -1180,6 +1198,19 @@ class Havoc:
             d_cells = torch.zeros((height // 4) * (width // 4) * CELL_DT.itemsize, dtype=torch.uint8, device=self.device)
         self.cqt_block_cells_d(width, height, min_cb_log2, qp, dpb0, dpb1, d_cqt, d_cells, width // 4)
         return self.down(d_cells, np.uint8).view(CELL_DT).reshape(height // 4, width // 4).copy()
+
+    def cqt_motion_store_d(self, width, height, min_cb_log2, poc, ref_poc0, ref_poc1, cqt_cells, store):
+        """cqt_commit_d's cell map as the collocated motion store: (height + 15) // 16 dense rows of (width + 15) // 16 COL_CELL_DT records, every one written
+        (havoc_mi355x_cqt_motion_store); cqt_cells, store: uint8 tensors.  No sync."""
+        self._ck(self.L.havoc_mi355x_cqt_motion_store(self.h, int(width), int(height), int(min_cb_log2), int(poc), int(ref_poc0), int(ref_poc1), _ptr(cqt_cells),
+                                                      _ptr(store)))
+
+    def temporal_candidates_d(self, params, store, store_stride, pus, n, out):
+        """the temporal candidate of n prediction units per list (havoc_mi355x_temporal_candidates): params: one TEMPORAL_PARAMS_DT record (read during the call);
+        store: uint8 tensor of COL_CELL_DT rows store_stride records apart; pus: uint8 tensor of workload.PICTURE_PU_DT [n]; out: uint8 tensor of TEMPORAL_CAND_DT
+        [2 n], index 2 * pu + list.  No sync."""
+        params = np.ascontiguousarray(params, TEMPORAL_PARAMS_DT).reshape(1)
+        self._ck(self.L.havoc_mi355x_temporal_candidates(self.h, params.ctypes.data, _ptr(store), int(store_stride), _ptr(pus), int(n), _ptr(out)))
 
     def unit_pred_ssd_d(self, bit_depth, src_y, src_stride, src_c, src_stride_c, pred_y, pred_stride, pred_c, pred_stride_c, jobs, out):
         """SSD(source, prediction) of units' luma, Cb and Cr blocks in one launch (havoc_mi355x_unit_pred_ssd); jobs: uint8 tensor of PRED_SSD_JOB_DT; out: int32 [3 n].

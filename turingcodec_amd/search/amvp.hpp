@@ -54,9 +54,16 @@ HAVOC_HD inline bool colocatedVector(const ColocatedCell &c, int X, int colPoc, 
     if (!c.predFlag[0] && !c.predFlag[1]) return false;
     // which of the cell's vectors: its only one; with two, the current list's when every reference picture lies in the past, else the list the collocated picture is NOT taken from
     const int listCol = !c.predFlag[0] ? 1 : (!c.predFlag[1] ? 0 : (allBackwards ? X : (collocatedFromL0 ? 1 : 0)));
-    if (c.longTerm[listCol]) return false;      // (the target is a short-term picture: the reference encoder has no others)
-    const int colPocDiff = colPoc - c.refPoc[listCol], currPocDiff = curPoc - targetPoc;
-    *out = colPocDiff == currPocDiff ? c.mv[listCol] : amvpDistScale(c.mv[listCol], colPocDiff, currPocDiff);
+    // (selects, not c.x[listCol]: on the device a record indexed by a run-time value leaves the registers -- the compiler moved both cells into LDS)
+    const bool colLongTerm = listCol ? c.longTerm[1] : c.longTerm[0];
+    const int colRefPoc = listCol ? c.refPoc[1] : c.refPoc[0];
+    const Mv colMv = listCol ? c.mv[1] : c.mv[0];
+    if (colLongTerm) return false;      // (the target is a short-term picture: the reference encoder has no others)
+    const int colPocDiff = colPoc - colRefPoc, currPocDiff = curPoc - targetPoc;
+    // THIS PROJECT'S OWN RULE: a vector that points into the collocated picture itself (distance 0) counts as no motion.  The reference would divide by zero in
+    // distScale; no conforming stream has the case (a picture does not predict from itself), so no trace can show it.
+    if (colPocDiff == 0) return false;
+    *out = colPocDiff == currPocDiff ? colMv : amvpDistScale(colMv, colPocDiff, currPocDiff);
     return true;
 }
 
@@ -71,6 +78,70 @@ HAVOC_HD inline bool deriveTemporalCandidate(int xPb, int yPb, int nPbW, int nPb
         available = colocatedVector(bottomRight, X, colPoc, curPoc, targetPoc, allBackwards, collocatedFromL0, out);
     if (!available) available = colocatedVector(centre, X, colPoc, curPoc, targetPoc, allBackwards, collocatedFromL0, out);
     return available;
+}
+
+// ---- the collocated motion store as plain data (turing/StateCollocatedMotion.h:51-122): one record per 16x16 luma samples, the motion of the unit that contains the
+// area's top-left sample.  = havoc_mi355x_col_cell, 24 bytes; havoc_mi355x_cqt_motion_store writes it (host form: cqt_decision.hpp's cqtMotionStore),
+// havoc_mi355x_temporal_candidates reads it through the two functions below -- the same text on the host and inside k_temporal_candidates.
+struct ColStoreCell
+{
+    int16_t mv[2][2];
+    int32_t refPoc[2];
+    uint8_t predFlag[2], longTerm[2];
+    uint32_t reserved;
+};
+
+HAVOC_HD inline ColocatedCell colocatedCellOf(const ColStoreCell &s)
+{
+    ColocatedCell c;
+    HAVOC_UNROLL
+    for (int l = 0; l < 2; ++l)
+    {
+        c.predFlag[l] = s.predFlag[l] != 0;
+        c.mv[l] = Mv(s.mv[l][0], s.mv[l][1]);
+        c.refPoc[l] = s.refPoc[l];
+        c.longTerm[l] = s.longTerm[l] != 0;
+    }
+    return c;
+}
+
+struct TemporalParams           // = havoc_mi355x_temporal_params, 48 bytes
+{
+    int32_t picWidth, picHeight, ctbLog2, colPoc, curPoc, targetPoc[2], allBackwards, collocatedFromL0, reserved[3];
+};
+struct TemporalCand             // = havoc_mi355x_temporal_cand, 8 bytes
+{
+    int16_t mv[2], available, source;       // source: 0 none, 1 the bottom-right cell, 2 the centre cell
+};
+
+// where the two cells of a prediction unit lie in the store (in cells), and whether the rule consults the bottom-right one at all (Mvp.h:141-181): never a cell
+// outside the store for a unit inside the picture -- the bottom-right cell is consulted only inside the picture, the centre sample is the unit's own
+HAVOC_HD inline bool temporalBottomRightConsulted(int x0, int y0, int w, int h, const TemporalParams &P)
+{
+    return (y0 >> P.ctbLog2) == ((y0 + h) >> P.ctbLog2) && y0 + h < P.picHeight && x0 + w < P.picWidth;
+}
+HAVOC_HD inline bool temporalPuInside(int x0, int y0, int w, int h, const TemporalParams &P)
+{
+    return x0 >= 0 && y0 >= 0 && w > 0 && h > 0 && w <= P.picWidth - x0 && h <= P.picHeight - y0;
+}
+
+// one record of havoc_mi355x_temporal_candidates: deriveTemporalCandidate over the two cells as stored, and which of them gave the vector.  bottomRight is read only
+// when consulted (hand in any cell otherwise).  A unit that is not inside the picture has no candidate
+HAVOC_HD inline TemporalCand temporalCandidateOf(int x0, int y0, int w, int h, const TemporalParams &P, const ColStoreCell &bottomRight, const ColStoreCell &centre, int X)
+{
+    TemporalCand r = {{0, 0}, 0, 0};
+    if (!temporalPuInside(x0, y0, w, h, P)) return r;
+    const ColocatedCell br = colocatedCellOf(bottomRight), ce = colocatedCellOf(centre);
+    const bool back = P.allBackwards != 0, fromL0 = P.collocatedFromL0 != 0;
+    const int target = X ? P.targetPoc[1] : P.targetPoc[0];
+    Mv v, unused;
+    const bool available = deriveTemporalCandidate(x0, y0, w, h, P.picWidth, P.picHeight, P.ctbLog2, br, ce, X, P.colPoc, P.curPoc, target, back, fromL0, &v);
+    const bool fromBr = temporalBottomRightConsulted(x0, y0, w, h, P) && colocatedVector(br, X, P.colPoc, P.curPoc, target, back, fromL0, &unused);
+    r.mv[0] = available ? v.x : int16_t(0);
+    r.mv[1] = available ? v.y : int16_t(0);
+    r.available = available ? 1 : 0;
+    r.source = int16_t(available ? (fromBr ? 1 : 2) : 0);
+    return r;
 }
 
 // nb[0..4] = A0 (below-left), A1 (left), B0 (above-right), B1 (above), B2 (above-left); X = the list being predicted, curPoc / targetPoc = the picture order counts of

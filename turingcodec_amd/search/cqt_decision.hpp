@@ -367,4 +367,39 @@ inline void cqtBlockCells(int width, int height, int minCbLog2, int qp, int dpb0
         }
 }
 
+// ---- the committed cells as the collocated motion store (turing/StateCollocatedMotion.h:51-122): what the NEXT picture's temporal candidate is derived from.
+// havoc_mi355x_cqt_motion_store does this in one launch, byte for byte; this is its host form, data-only.  fillRectangle (:75-90) writes entry (X, Y) for every
+// x0 <= 16 X < x1, y0 <= 16 Y < y1 of a unit: the entry holds the motion of the unit that CONTAINS luma sample (16 X, 16 Y) -- an 8x8 unit off the 16-grid writes
+// none, a 64x64 unit sixteen -- and the final units partition a CTU, so the cell that covers that sample names the one writer.
+struct CqtColCell           // = havoc_mi355x_col_cell = amvp.hpp's ColStoreCell, 24 bytes
+{
+    int16_t mv[2][2];
+    int32_t refPoc[2];
+    uint8_t predFlag[2], longTerm[2];
+    uint32_t reserved;
+};
+
+// cqt: (height >> minCbLog2) rows of (width >> minCbLog2) committed cells; store: (height + 15) / 16 dense rows of (width + 15) / 16 records, every one written.
+// refPoc0 / refPoc1: the picture order counts of the pictures behind lists 0 and 1 (reference index 0).  An undecided CTU's entries are "not available" (all zero),
+// as the reference's default PuData is
+inline void cqtMotionStore(int width, int height, int minCbLog2, int refPoc0, int refPoc1, const CqtCommitCell *cqt, CqtColCell *store)
+{
+    const int wc = width >> minCbLog2, sw = (width + 15) / 16, sh = (height + 15) / 16;
+    for (int Y = 0; Y < sh; ++Y)
+        for (int X = 0; X < sw; ++X)
+        {
+            const CqtCommitCell &q = cqt[long(16 * Y >> minCbLog2) * wc + (16 * X >> minCbLog2)];
+            CqtColCell c = {{{0, 0}, {0, 0}}, {0, 0}, {0, 0}, {0, 0}, 0};
+            if (q.unit >= 0)
+                for (int l = 0; l < 2; ++l)
+                    if (q.pred != 1 - l)       // 0 L0, 1 L1, 2 bi
+                    {
+                        c.predFlag[l] = 1;
+                        c.mv[l][0] = q.mv[l][0], c.mv[l][1] = q.mv[l][1];
+                        c.refPoc[l] = l ? refPoc1 : refPoc0;
+                    }
+            store[long(Y) * sw + X] = c;
+        }
+}
+
 } // namespace havoc_search
