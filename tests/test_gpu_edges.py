@@ -139,8 +139,8 @@ def test_prediction_writes_exactly_the_block(hv, data):
 
 
 def test_reconstruction_in_place(hv, data, oracle):
-    """inverse_transform_add and tu_reconstruct with pred == dst (the intra path reconstructs into the plane it
-    predicted into)"""
+    """inverse_transform_add with pred == dst, nine 16x16 blocks of an 8-bit plane (the intra path reconstructs into the plane it
+    predicted into).  tu_reconstruct in place: tests/test_tu_chain.py::test_reconstruct_in_place, every size and sample width"""
     rng = np.random.default_rng(8)
     n, log2 = 16, 4
     m = 9
