@@ -1428,6 +1428,20 @@ int havoc_mi355x_search_picture_uni(havoc_mi355x_ctx *ctx, int S, const havoc_mi
  * blocks what is queued behind it -- give the delivering stream another priority (hipStreamCreateWithPriority: fine for a few such streams; the high-priority pool is
  * small) or, for many, raise GPU_MAX_HW_QUEUES to about the device's two dozen and keep one priority (bench.py --vr-bands; profiles/r05/banded_pipeline.txt). */
 int havoc_mi355x_search_gate(havoc_mi355x_ctx *ctx, const int32_t *d_rows_ready);
+/* The TEMPORAL motion vector candidate in the picture search's predictor derivation (turing/Mvp.h:195-436 consults it where the two spatial predictors A and B do not
+ * already give two different ones; turingcodec_amd/search/picture_order.hpp: derivePredictors hands it to deriveAmvp).  d_cands = havoc_mi355x_temporal_cand[2 * n_pus]
+ * on the device, index 2 * pu + list: the layout havoc_mi355x_temporal_candidates writes for the same d_pus -- the vector is used as written there (already scaled to the
+ * target picture's distance; nothing is scaled or clamped here), `available` == 0 means no candidate, `source` is not read.  The havoc_mi355x_search_picture_uni launches
+ * of this context that follow read d_cands[2 * pu + list] once per (unit, list) -- both step_launches forms, with or without d_out_bi (the refinement runs with the
+ * predictors the uni-directional search ran with, so it follows) -- and must be called with the same n_pus: another count is HAVOC_MI355X_EINVAL there.  The records must
+ * be complete in stream order before the search is launched.  d_cands = NULL removes the table: the searches are then, launch for launch and byte for byte, those without
+ * this call (kernels compiled without the table).  HAVOC_MI355X_EINVAL for d_cands != NULL with n_pus <= 0 and for a pointer that is not 8-byte aligned.  The table is read,
+ * never written; the call allocates nothing, launches nothing and synchronises nothing, so it can be made while a stream is being captured.  Independent of
+ * havoc_mi355x_search_gate: either, both or neither may be set.
+ * Any int16 components are safe: a predictor is only read FROM after LimitFullPelMv limited it to the picture's surroundings (decision.hpp: fullPel; the kernel's
+ * window staging restates it), so no sample is read outside the ctb_size + 20 the planes own; unlimited it enters only the mvd arithmetic, whose int16 wrap-around is
+ * the same text on host and device.  The launch + host-replay client (libhavoc_search.so: havoc_search_picture_uni) does not know the table. */
+int havoc_mi355x_search_temporal(havoc_mi355x_ctx *ctx, const havoc_mi355x_temporal_cand *d_cands, int n_pus);
 /* The PRODUCER's side of the same rule (turing/TaskDeblock.cpp:151-167 deblocks and publishes a picture's rows while the rows below are still being encoded): a launch on
  * THIS context's stream that ends when CTU rows 0 .. ctu_row of both lists of the havoc_mi355x_search_picture_uni running over d_work (its workspace; one-launch form) on
  * ANOTHER stream are done -- whatever is queued behind it (the band's predictions, transform trees, deblocking, padding, the counter a dependent picture's search_gate

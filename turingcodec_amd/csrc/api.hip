@@ -678,10 +678,21 @@ int havoc_mi355x_search_picture_uni(havoc_mi355x_ctx *ctx, int S, const havoc_mi
     REQUIRE(params->bit_depth >= 8 && params->bit_depth <= (S == 1 ? 8 : 10), "bit_depth must be 8 (S=1) or 8..10 (S=2)");
     REQUIRE(!ctx->searchGate || (params->concurrent_frames > 1 && !step_launches),
             "search gate: needs concurrent_frames > 1 (only then are the vectors of a CTU row limited to rows the gate can promise) and the one-launch form");
+    REQUIRE(!ctx->searchTemporal || ctx->searchTemporalPus == n_pus, "search temporal: the table was set for another number of prediction units than n_pus");
     const long ro[2] = {(long)ref_origin[0], (long)ref_origin[1]}, po[2] = {(long)phase_origin[0], (long)phase_origin[1]};
     return check(launch_search_picture_uni(LS(ctx), S, params, mvp_rate, d_src, (long)src_origin, src_stride, d_ref, ro, ref_stride, d_phase, plane_elems, po, d_pus,
-                                           d_ctu_first, ctus_x, ctus_y, n_pus, d_out, d_out_bi, d_field, d_work, step_launches, ctx->searchGate),
+                                           d_ctu_first, ctus_x, ctus_y, n_pus, d_out, d_out_bi, d_field, d_work, step_launches, ctx->searchGate, ctx->searchTemporal),
                  "search_picture_uni");
+}
+
+int havoc_mi355x_search_temporal(havoc_mi355x_ctx *ctx, const havoc_mi355x_temporal_cand *d_cands, int n_pus)
+{
+    REQUIRE_CTX();
+    REQUIRE(!d_cands || n_pus > 0, "n_pus must be positive with a table");
+    REQUIRE(((uintptr_t)d_cands & 7) == 0, "d_cands must be 8-byte aligned");
+    ctx->searchTemporal = d_cands;
+    ctx->searchTemporalPus = d_cands ? n_pus : 0;
+    return 0;
 }
 
 int havoc_mi355x_search_gate(havoc_mi355x_ctx *ctx, const int32_t *d_rows_ready)

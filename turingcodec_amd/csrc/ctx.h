@@ -26,6 +26,8 @@ struct havoc_mi355x_ctx
     void *flagD = nullptr;
     uint32_t flagSeq = 0;
     const int32_t *searchGate = nullptr;      // havoc_mi355x_search_gate: rows of the reference pictures that have arrived, [2] device ints (nullptr: references complete)
+    const void *searchTemporal = nullptr;     // havoc_mi355x_search_temporal: havoc_mi355x_temporal_cand[2 * searchTemporalPus] on the device (nullptr: no temporal candidate)
+    int searchTemporalPus = 0;
 };
 
 // the stream the next launch is issued on

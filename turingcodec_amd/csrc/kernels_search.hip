@@ -56,6 +56,16 @@ struct SearchArgs
     const int *rowsReady;                     // [2] or nullptr: luma rows (from picture row 0) of reference list l that are final in ref[l] AND in all of phase[l], raised
                                               // by another stream while this kernel runs (havoc_mi355x_search_gate): a CTU row waits for what its vectors can reach
 };
+// ... and with the units' temporal candidates (havoc_mi355x_search_temporal).  A record of its own, the argument of the <S, true> kernels alone: the kernels without a
+// table keep the argument block, and with it the code, they had
+struct SearchArgsTemporal : SearchArgs
+{
+    const havoc_search::TemporalCand *temporal;      // [2 * pu + list]
+};
+template <bool T> struct SearchArgsOf { typedef SearchArgs type; };
+template <> struct SearchArgsOf<true> { typedef SearchArgsTemporal type; };
+__device__ __forceinline__ const havoc_search::TemporalCand *temporalOf(const SearchArgs &) { return nullptr; }
+__device__ __forceinline__ const havoc_search::TemporalCand *temporalOf(const SearchArgsTemporal &a) { return a.temporal; }
 
 // LDS operands are named by address-space-3 pointers so that they are read with ds_read (a generic pointer would be a flat load)
 typedef const __attribute__((address_space(3))) char *LdsPtr;
@@ -1043,9 +1053,11 @@ __device__ __forceinline__ void stage_uni(const SearchArgs &a, Lds<S> &x, Device
     }
 }
 
-// one CTU's searches in one list.  x.mv / x.valid [256 ..]: the cells left of and above the CTU, put there by the caller
-template <int S>
-__device__ __forceinline__ void search_ctu(const SearchArgs &a, Lds<S> &x, CtuStage<S> &cs, const int list, const int cx, const int cy, Mv &mvPrev)
+// one CTU's searches in one list.  x.mv / x.valid [256 ..]: the cells left of and above the CTU, put there by the caller.  T (a compile-time choice: the kernels
+// without a table are the code they were): each derivation also receives temporal[2 * p + list]
+template <int S, bool T>
+__device__ __forceinline__ void search_ctu(const SearchArgs &a, Lds<S> &x, CtuStage<S> &cs, const int list, const int cx, const int cy, Mv &mvPrev,
+                                           const havoc_search::TemporalCand *temporal)
 {
     const int c = cy * a.ctusX + cx, tid = threadIdx.x;
     const int ctb = a.sp.ctbSize, xCtb = cx * ctb, yCtb = cy * ctb;
@@ -1083,7 +1095,19 @@ __device__ __forceinline__ void search_ctu(const SearchArgs &a, Lds<S> &x, CtuSt
 #endif
         const havoc_picture_pu q = a.pus[p];
         Mv mvp[2];
-        havoc_search::derivePredictors(q, list, ctb, a.sp.picWidth, a.sp.picHeight, get, mvp);
+        if constexpr (T)
+        {   // p and list are the workgroup's: one 8-byte record, the same for every lane, kept in scalar registers like the cells `get` reads (no LDS, nothing indexed)
+            const u32x2 raw = *reinterpret_cast<const u32x2 *>(temporal + (2 * p + list));
+            const uint32_t lo = __builtin_amdgcn_readfirstlane(raw.x), hi = __builtin_amdgcn_readfirstlane(raw.y);
+            havoc_search::TemporalCand cand;
+            cand.mv[0] = int16_t(lo & 0xffff);
+            cand.mv[1] = int16_t(lo >> 16);
+            cand.available = int16_t(hi & 0xffff);
+            cand.source = int16_t(hi >> 16);
+            havoc_search::derivePredictors(q, list, ctb, a.sp.picWidth, a.sp.picHeight, get, mvp, &cand);
+        }
+        else
+            havoc_search::derivePredictors(q, list, ctb, a.sp.picWidth, a.sp.picHeight, get, mvp);
         const havoc_search::PuContext pu = havoc_search::contextOf(q, ctb, mvp, a.mvpRate, mvPrev);
         DeviceView<S> view;
         stage_uni<S>(a, x, view, pu, list, &cs, &box);
@@ -1345,8 +1369,8 @@ __device__ __forceinline__ void load_neighbours(const SearchArgs &a, Lds<S> &x, 
 }
 
 // (a) one launch per wavefront step: the CTUs with cx + 2 cy == step
-template <int S>
-__global__ __launch_bounds__(kThreads) void k_search_step(const SearchArgs a, const int step, const int yLo)
+template <int S, bool T>
+__global__ __launch_bounds__(kThreads) void k_search_step(const typename SearchArgsOf<T>::type a, const int step, const int yLo)
 {
     __shared__ Lds<S> x;
     __shared__ CtuStage<S> cs;
@@ -1359,7 +1383,7 @@ __global__ __launch_bounds__(kThreads) void k_search_step(const SearchArgs a, co
     load_neighbours<S>(a, x, list, cx, cy, true, true);
     __syncthreads();
     Mv mvPrev = cx ? havoc_search::MotionField::unpack(a.rowPrev[2 * cy + list]) : Mv(0, 0);
-    search_ctu<S>(a, x, cs, list, cx, cy, mvPrev);
+    search_ctu<S, T>(a, x, cs, list, cx, cy, mvPrev, temporalOf(a));
     if (tid == 0) a.rowPrev[2 * cy + list] = havoc_search::MotionField::pack(mvPrev);
 }
 
@@ -1369,8 +1393,8 @@ __global__ __launch_bounds__(kThreads) void k_search_step(const SearchArgs a, co
 // (it cannot, short of a fault elsewhere) gives up after kSpinLimit polls and raises a flag the host reads: nothing hangs.
 constexpr int kSpinLimit = 1 << 22;
 
-template <int S>
-__global__ __launch_bounds__(kThreads) void k_search_rows(const SearchArgs a)
+template <int S, bool T>
+__global__ __launch_bounds__(kThreads) void k_search_rows(const typename SearchArgsOf<T>::type a)
 {
     __shared__ Lds<S> x;
     __shared__ CtuStage<S> cs;
@@ -1462,7 +1486,7 @@ __global__ __launch_bounds__(kThreads) void k_search_rows(const SearchArgs a)
         }
         load_neighbours<S>(a, x, list, cx, cy, false, true);      // the cells above, now final; the cells to the left were kept below
         __syncthreads();
-        search_ctu<S>(a, x, cs, list, cx, cy, mvPrev);
+        search_ctu<S, T>(a, x, cs, list, cx, cy, mvPrev, temporalOf(a));
         // this CTU's right column becomes the next one's left neighbours; its own cells start undecided
         const int32_t keepMv = tid < 16 ? x.mv[tid * 16 + 15] : 0;
         const uint8_t keepValid = tid < 16 ? x.valid[tid * 16 + 15] : 0;
@@ -1487,7 +1511,39 @@ __global__ __launch_bounds__(kThreads) void k_search_rows(const SearchArgs a)
     }
 }
 
+// the walk's launches: one (rows wait for each other in the kernel), or -- stepLaunches -- ctusX + 2 * (ctusY - 1) on the stream
+template <bool T>
+hipError_t launch_walk(hipStream_t st, int S, const typename SearchArgsOf<T>::type &a, int stepLaunches)
+{
+    const int ctusX = a.ctusX, ctusY = a.ctusY;
+    if (!stepLaunches)
+    {
+        hipLaunchKernelGGL((S == 1 ? k_search_rows<1, T> : k_search_rows<2, T>), dim3(2 * ctusY), dim3(kThreads), 0, st, a);
+        return hipGetLastError();
+    }
+    for (int step = 0; step <= ctusX - 1 + 2 * (ctusY - 1); ++step)
+    {
+        const int yLo = step > ctusX - 1 ? (step - (ctusX - 1) + 1) / 2 : 0, yHi = step / 2 < ctusY - 1 ? step / 2 : ctusY - 1;
+        if (yHi < yLo) continue;
+        const dim3 grid(2 * (yHi - yLo + 1));
+        hipLaunchKernelGGL((S == 1 ? k_search_step<1, T> : k_search_step<2, T>), grid, dim3(kThreads), 0, st, a, step, yLo);
+    }
+    return hipGetLastError();
+}
+
 } // namespace
+
+#ifdef HAVOC_SEARCH_TEMPORAL_UNIT
+// kernels_search_temporal.hip: this file once more, for the walk kernels that read a table of temporal candidates and nothing else.  A translation unit of their own:
+// compiled beside them, the kernels without a table came out of the compiler as different code (DESIGN.md f2^11) -- apart, they are the instructions they were.
+hipError_t launch_search_walk_temporal(hipStream_t st, int S, const void *searchArgs, const void *temporal, int stepLaunches)
+{
+    SearchArgsTemporal at;
+    static_cast<SearchArgs &>(at) = *static_cast<const SearchArgs *>(searchArgs);
+    at.temporal = static_cast<const havoc_search::TemporalCand *>(temporal);
+    return launch_walk<true>(st, S, at, stepLaunches);
+}
+#else
 
 hipError_t launch_search_list(hipStream_t st, int S, const havoc_mi355x_search_params *sp, const void *src, long srcOrigin, long srcStride, const void *ref, long refOrigin,
                               long refStride, const void *phase, long planeElems, long phaseOrigin, const void *pus, int n, void *out)
@@ -1602,13 +1658,13 @@ static hipError_t launch_bi(hipStream_t st, int S, const SearchArgs &a, int nPus
     return hipGetLastError();
 }
 
-// the whole picture: one launch (rows wait for each other in the kernel), or -- stepLaunches -- ctusX + 2 * (ctusY - 1) launches on the stream
+// the whole picture: the zeroed workspace and field, the walk (launch_walk), the refinement launches
 static_assert(sizeof(havoc_mi355x_search_params) == sizeof(havoc_search_params) && sizeof(havoc_search_params) == 48, "search ABI");
 
 hipError_t launch_search_picture_uni(hipStream_t st, int S, const havoc_mi355x_search_params *sp, const int64_t mvpRate[2], const void *src, long srcOrigin, long srcStride,
                                      const void *ref, const long refOrigin[2], long refStride, const void *phase, long planeElems, const long phaseOrigin[2], const void *pus,
                                      const int32_t *ctuFirst, int ctusX, int ctusY, int nPus, void *out, void *outBi, int16_t *field, void *work, int stepLaunches,
-                                     const int32_t *rowsReady)
+                                     const int32_t *rowsReady, const void *temporal)
 {
     SearchArgs a;
     a.rowsReady = rowsReady;
@@ -1656,25 +1712,12 @@ hipError_t launch_search_picture_uni(hipStream_t st, int S, const havoc_mi355x_s
     hipError_t e = hipMemsetAsync(work, 0, search_workspace_bytes(sp->pic_width, sp->pic_height), st);
     if (e != hipSuccess) return e;
     if ((e = hipMemsetAsync(field, 0, 2 * cells * 4, st)) != hipSuccess) return e;
-    if (!stepLaunches)
-    {
-        if (S == 1)
-            hipLaunchKernelGGL(k_search_rows<1>, dim3(2 * ctusY), dim3(kThreads), 0, st, a);
-        else
-            hipLaunchKernelGGL(k_search_rows<2>, dim3(2 * ctusY), dim3(kThreads), 0, st, a);
-        return launch_bi(st, S, a, nPus);
-    }
-    for (int step = 0; step <= ctusX - 1 + 2 * (ctusY - 1); ++step)
-    {
-        const int yLo = step > ctusX - 1 ? (step - (ctusX - 1) + 1) / 2 : 0, yHi = step / 2 < ctusY - 1 ? step / 2 : ctusY - 1;
-        if (yHi < yLo) continue;
-        const dim3 grid(2 * (yHi - yLo + 1));
-        if (S == 1)
-            hipLaunchKernelGGL(k_search_step<1>, grid, dim3(kThreads), 0, st, a, step, yLo);
-        else
-            hipLaunchKernelGGL(k_search_step<2>, grid, dim3(kThreads), 0, st, a, step, yLo);
-    }
+    // with a table of temporal candidates: the kernels that read it (kernels_search_temporal.hip); without one, the kernels that do not know of it
+    e = temporal ? launch_search_walk_temporal(st, S, &a, temporal, stepLaunches) : launch_walk<false>(st, S, a, stepLaunches);
+    if (e != hipSuccess) return e;
     return launch_bi(st, S, a, nPus);
 }
+
+#endif
 
 } // namespace havoc_gpu

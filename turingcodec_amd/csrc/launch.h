@@ -100,7 +100,9 @@ hipError_t launch_search_list(hipStream_t, int S, const havoc_mi355x_search_para
 hipError_t launch_search_bi_list(hipStream_t, int S, const havoc_mi355x_search_params *, const void *, long, long, const void *, long, long, const void *, long, long, const void *,
                                  long, const void *, const int16_t *, int, void *);
 hipError_t launch_search_picture_uni(hipStream_t, int S, const havoc_mi355x_search_params *, const int64_t *, const void *, long, long, const void *, const long *, long,
-                                     const void *, long, const long *, const void *, const int32_t *, int, int, int, void *, void *, int16_t *, void *, int, const int32_t *);
+                                     const void *, long, const long *, const void *, const int32_t *, int, int, int, void *, void *, int16_t *, void *, int, const int32_t *,
+                                     const void *temporal);
+hipError_t launch_search_walk_temporal(hipStream_t, int S, const void *searchArgs, const void *temporal, int stepLaunches);
 hipError_t launch_search_wait_rows(hipStream_t, const void *, int, int, int, int *);
 hipError_t launch_sao_stats(hipStream_t, int S, int bd, const void *, long, const void *, long, const havoc_mi355x_sao_stats_job *, int, int64_t *);
 hipError_t launch_sao_band_chroma(hipStream_t, int S, int bd, const void *, long, const void *, long, const havoc_mi355x_sao_chroma_job *, int, int64_t *);

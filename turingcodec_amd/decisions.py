@@ -463,7 +463,7 @@ class DecisionPicture:
 
     def __init__(self, hv, width, height, bit_depth=8, qp=32, seed=11, threads=16, frames=None, density=1.0, intra=True, search_on_device=True, distance=1,
                  sao=False, residual_rates=False, tree_rates=False, pu_modes=False, cu_close=False, cqt=False, unit_trees=False, commit=False, finish=False,
-                 motion=None, col=None):
+                 motion=None, col=None, temporal_mvp=False):
         """motion=(poc, ref_poc0, ref_poc1) (needs commit=True): the committed picture also leaves its collocated motion store in `cqt_store`
         (havoc_mi355x_cqt_motion_store, directly behind the commit inside the replayed graph; cqt_motion_results()) -- with finish=True the two things a reference
         picture is.
@@ -471,12 +471,18 @@ class DecisionPicture:
         collocated_from_l0=) (device search route only): the temporal candidate of every unit of self.pus per list from that store
         (havoc_mi355x_temporal_candidates, inside the replayed graph; temporal_candidates()).  The store belongs to ANOTHER picture: that the step which writes it
         has finished (or is ordered before this picture's step on the same stream) is the caller's to establish, and the tensor must stay alive and in place --
-        the recorded graph holds its address.  The candidates are produced, not yet consumed: the search walk's predictors do not read them."""
+        the recorded graph holds its address.  With col= alone the candidates are produced, not consumed: the search walk's predictors do not read them.
+        temporal_mvp=True (needs col=; not step_banded): the search walk's predictor derivation consumes them (havoc_mi355x_search_temporal; picture_order.hpp:
+        derivePredictors).  step() then issues temporal_launch() BEFORE the searches, on the context's stream and outside the replayed graph (not again inside it), sets
+        the table on the context for the search and removes it afterwards -- also when the search raises; temporal_candidates() returns the records as before.  What
+        follows the searches (pu_candidates, pu_rate, cu_close, cqt, the commit, the motion store) reads their results in place and needs nothing of its own."""
         import torch
         if motion is not None and not commit:
             raise ValueError("motion=(poc, ref_poc0, ref_poc1) makes the collocated motion store of the committed picture: it needs commit=True")
         if col is not None and not search_on_device:
             raise ValueError("col= needs the device route (search_on_device=True)")
+        if temporal_mvp and col is None:
+            raise ValueError("temporal_mvp=True feeds the temporal candidates of col= into the search walk's predictors: it needs col=")
         if finish and not commit:
             raise ValueError("finish=True deblocks and pads the committed picture: it needs commit=True")
         if commit and not (unit_trees and cqt):
@@ -534,6 +540,7 @@ class DecisionPicture:
         self.motion = None if motion is None else tuple(int(v) for v in motion)
         # this picture's own temporal candidates from ANOTHER picture's store (havoc_mi355x_temporal_candidates): the caller's dict or None
         self.col = None if col is None else dict(col)
+        self.temporal_mvp = bool(temporal_mvp)      # ... consumed by the search walk's predictor derivation (havoc_mi355x_search_temporal)
         self.sao = sao                               # in-loop SAO between deblocking and padding (sao_filter_inputs / sao_loop_filter)
         from . import havoc as hmod
         from . import workload
@@ -1786,7 +1793,16 @@ class DecisionPicture:
 
     def step(self):
         self.phase_planes()
-        res, field, stats = self.search()
+        if self.temporal_mvp:
+            # the candidates before the searches that read them, on the same stream; the table is the context's only while this picture's walk runs
+            self.temporal_launch()
+            self.hv.search_temporal_d(self._d_temporal, len(self.pus))
+            try:
+                res, field, stats = self.search()
+            finally:
+                self.hv.search_temporal_d(None, 0)
+        else:
+            res, field, stats = self.search()
         if self.intra_parts:
             # (running this on a second context / stream beside the searches -- it reads nothing they decide -- was measured: one picture alone 15.7 -> 15.5 ms, but
             # 294 -> 268 / 383 -> 237 pictures/s with 8 / 16 in flight: a second issuing thread per picture costs more than the overlap gives)
@@ -1806,7 +1822,8 @@ class DecisionPicture:
             pu += (self.cqt_commit_launch,) if self.commit else ()       # (directly behind the quadtree: it acts on its records, into buffers of its own)
             pu += (self.cqt_motion_launch,) if self.motion is not None else ()      # (directly behind the commit: it reads the cells that wrote, nothing else)
             pu += (self.cqt_finish_launch,) if self.finish else ()       # (behind the commit: it filters and pads what that wrote, in place)
-            pu += (self.temporal_launch,) if self.col is not None else ()           # (reads another picture's store and this picture's unit table only)
+            pu += (self.temporal_launch,) if self.col is not None and not self.temporal_mvp else ()      # (reads another picture's store and this picture's unit table
+                                                                                                         # only; with temporal_mvp it ran before the searches)
             if self.sao:
                 self._replayed("after the searches", lambda: (self.merge_candidates(field), self.predict(field), self.sao_filter_inputs(field),
                                                               self.sao_loop_filter(), [f() for f in pu]))

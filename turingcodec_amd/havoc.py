@@ -116,6 +116,7 @@ def _load():
         "search_motion_bi": [_vp, _i, _vp, _vp, C.c_int64, _ip, _vp, C.c_int64, _ip, _vp, _ip, C.c_int64, _vp, C.c_int64, _vp, _vp, _i, _vp],
         "search_picture_uni": [_vp, _i, _vp, _vp, _vp, C.c_int64, _ip, _vp, _vp, _ip, _vp, _ip, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i],
         "search_gate": [_vp, _vp],
+        "search_temporal": [_vp, _vp, _i],
         "search_wait_rows": [_vp, _vp, _i, _i, _i, _vp],
         "block_cells_add": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp],
         "intra_order": [_vp, _vp, _vp, _i, C.c_int32, _vp, _vp, _vp, _vp],
@@ -722,6 +723,13 @@ class Havoc:
         device tensor of 2 (rows of list 0 / list 1 that are final in the picture and its 16 phase planes, raised on another stream); None removes the gate"""
         self._gate = rows_ready      # (kept alive)
         self._ck(self.L.havoc_mi355x_search_gate(self.h, _ptr(rows_ready) if rows_ready is not None else None))
+
+    def search_temporal_d(self, cands, n_pus):
+        """havoc_mi355x_search_temporal: the picture searches this context launches from now on hand every derivation its temporal candidate -- cands = a uint8 device
+        tensor of TEMPORAL_CAND_DT [2 * n_pus], index 2 * pu + list, as temporal_candidates_d wrote it for the same units (read, never written; complete in stream order
+        before the search); None removes the table (n_pus is then ignored).  Nothing is launched.  Independent of search_gate."""
+        self._temporal = cands      # (kept alive)
+        self._ck(self.L.havoc_mi355x_search_temporal(self.h, _ptr(cands) if cands is not None else None, int(n_pus)))
 
     def search_wait_rows(self, work, width, height, ctu_row, gave_up):
         """havoc_mi355x_search_wait_rows: a launch on THIS context's stream that ends when CTU rows 0 .. ctu_row (both lists) of the picture search running over the workspace

@@ -6,7 +6,8 @@
 // rule, PINNED: the traced reference encoder records, for every searchUni call, the five neighbours as its neighbourPuData() returned them, the temporal candidate and the
 // two predictors it derived (the HAVOC_TRACE_AMVP trace point, inserted after Search.hpp:1779); tests/test_trace_pin.py requires deriveAmvp() to give the same two
 // predictors for every record of six encodes (0 differ); the temporal candidate is derived below from the collocated picture's cells and pinned likewise.  picture_order.hpp's walk -- on the host and inside k_search_rows -- derives its predictors with it, from the five
-// positions under the encoder's availability rules; the walk's neighbours are vectors of the same list into the same reference picture (no scaling, no temporal candidate).
+// positions under the encoder's availability rules; the walk's neighbours are vectors of the same list into the same reference picture (no scaling); the temporal candidate is the walk's optional input (TemporalCand
+// below, one record per (unit, list) as havoc_mi355x_temporal_candidates wrote it), absent unless the caller hands a table in.
 #pragma once
 
 #include "decision.hpp"

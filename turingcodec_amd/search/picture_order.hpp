@@ -11,8 +11,10 @@
 // (amvp.hpp: the five spatial candidates A0, A1, B0, B1, B2 of turing/Mvp.h:195-436, pinned against the encoder's own derivations), read at the positions
 // and under the availability rules of the encoder's neighbourPuData (turing/StateSpatial.h:208-246, Global.h:285-370: inside the picture, not in the next CTU
 // row, earlier than the PU in z-order).  What the walk still simplifies: a neighbour is a vector of the SAME list into the SAME reference picture (every PU is
-// searched in both lists with reference index 0, and the two lists' walks read nothing of each other: Search.hpp:1883-1884), so no candidate is scaled; there
-// is no temporal candidate.  The above-right neighbour B0 makes the wavefront's two-CTU lag a requirement (TaskEncodeSubstream.cpp:71-95).
+// searched in both lists with reference index 0, and the two lists' walks read nothing of each other: Search.hpp:1883-1884), so no spatial candidate is scaled.
+// The temporal candidate (Mvp.h:141-181) is an INPUT: a walk that is handed the records of havoc_mi355x_temporal_candidates (amvp.hpp: TemporalCand, one per (unit,
+// list), scaled there) passes each to deriveAmvp, which consults it where the rule does; a walk without such a table has no temporal candidate, as before f2^11.
+// The above-right neighbour B0 makes the wavefront's two-CTU lag a requirement (TaskEncodeSubstream.cpp:71-95).
 // What matters for the batch client is that the dependency is REAL: a PU's search cannot be replayed before its neighbours' vectors exist.
 #pragma once
 
@@ -137,9 +139,10 @@ HAVOC_HD inline bool neighbourPositionAvailable(const havoc_picture_pu &q, int c
     return precedesInZ(xCurr, yCurr - yCtbCurr, xN, yN - yCtbCurr);
 }
 
-// the two predictors of PU q in `list`, read through `get(list, x, y, &mv)` (false = nothing decided there)
+// the two predictors of PU q in `list`, read through `get(list, x, y, &mv)` (false = nothing decided there).  `temporal` = this (unit, list)'s temporal candidate as
+// havoc_mi355x_temporal_candidates wrote it -- already scaled to the target picture's distance, used as it stands -- or nullptr: no temporal candidate (the walk before f2^11)
 template <class Get>
-HAVOC_HD inline void derivePredictors(const havoc_picture_pu &q, int list, int ctb, int picW, int picH, Get get, Mv mvp[2])
+HAVOC_HD inline void derivePredictors(const havoc_picture_pu &q, int list, int ctb, int picW, int picH, Get get, Mv mvp[2], const TemporalCand *temporal = nullptr)
 {
     const int xN[5] = {q.x0 - 1, q.x0 - 1, q.x0 + q.w, q.x0 + q.w - 1, q.x0 - 1};                 // A0, A1, B0, B1, B2 (Mvp.h:219-222, 286-287)
     const int yN[5] = {q.y0 + q.h, q.y0 + q.h - 1, q.y0 - 1, q.y0 - 1, q.y0 - 1};
@@ -155,7 +158,7 @@ HAVOC_HD inline void derivePredictors(const havoc_picture_pu &q, int list, int c
             nb[k].mv[0] = v;                  // name does not enter the rule, so the records are filed under list 0 -- a constant index: indexed by `list` they went to scratch
         }                                     // memory on the device (112 bytes per lane, +2.6 ms per 1080p picture)
     }
-    deriveAmvp(0, 0, 0, nb, false, Mv(0, 0), mvp);
+    deriveAmvp(0, 0, 0, nb, temporal && temporal->available != 0, temporal ? Mv(temporal->mv[0], temporal->mv[1]) : Mv(0, 0), mvp);
 }
 
 HAVOC_HD inline PuContext contextOf(const havoc_picture_pu &q, int ctb, const Mv mvp[2], const Cost mvpRate[2], Mv mvPrevious2Nx2N)
@@ -184,6 +187,8 @@ HAVOC_HD inline PuContext contextOf(const havoc_picture_pu &q, int ctb, const Mv
 // vector, then list 1 against the prediction from list 0's REFINED vector.  bi(p, list, puContext, otherMv, startMv) -> BiResult;
 // outBi[2 * p + list] (mv, mvd, mvp_flag, calls, cost_subpel = cost; zero where no refinement runs).  The refined vectors do not enter the motion
 // field: which of uni / bi / merge a PU ends up with is the mode decision's (not restated), the field keeps the uni-directional vectors.
+// With `temporal` (havoc_mi355x_temporal_cand[2 * p + list], the records havoc_mi355x_temporal_candidates writes for the same units): each derivation receives its
+// (unit, list)'s temporal candidate.  The refinement gets the PuContext the uni-directional search ran with, so its predictors are the same ones.
 HAVOC_HD inline bool biRefined(const havoc_picture_pu &q) { return q.w + q.h != 12; }
 
 struct NoBi
@@ -193,7 +198,8 @@ struct NoBi
 
 template <class Search, class Bi = NoBi>
 void walkPictureSequential(const SearchParams &sp, const havoc_picture_pu *pus, const int32_t *ctuFirst, int ctusX, int ctusY, const Cost mvpRate[2],
-                           Search search, havoc_search_result *out, MotionField &field, Bi bi = Bi(), havoc_search_result *outBi = nullptr)
+                           Search search, havoc_search_result *out, MotionField &field, Bi bi = Bi(), havoc_search_result *outBi = nullptr,
+                           const TemporalCand *temporal = nullptr)
 {
     field.init(sp.picWidth, sp.picHeight);
     auto get = [&](int list, int x, int y, Mv *v) { return field.get(list, x, y, v); };
@@ -208,7 +214,7 @@ void walkPictureSequential(const SearchParams &sp, const havoc_picture_pu *pus, 
             for (int list = 0; list < 2; ++list)
             {
                 Mv mvp[2];
-                derivePredictors(pus[p], list, sp.ctbSize, sp.picWidth, sp.picHeight, get, mvp);
+                derivePredictors(pus[p], list, sp.ctbSize, sp.picWidth, sp.picHeight, get, mvp, temporal ? temporal + 2 * p + list : nullptr);
                 const PuContext pu = contextOf(pus[p], sp.ctbSize, mvp, mvpRate, mvPrev[list]);
                 const UniResult r = search(p, list, pu);
                 ctx[list] = pu;
