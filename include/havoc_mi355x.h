@@ -313,7 +313,9 @@ int havoc_mi355x_ssd(havoc_mi355x_ctx *ctx, int S, const void *d_a, intptr_t str
 int havoc_mi355x_satd(havoc_mi355x_ctx *ctx, int S, int max_w, int max_h, const void *d_a, intptr_t stride_a, const void *d_b,
                       intptr_t stride_b, const havoc_mi355x_pair_job *d_jobs, int njobs, int32_t *d_out);
 /* The same measure for one block `a` against `count` candidate blocks `b` (costDistortionMv's candidates of one PU,
- * turing/Search.hpp:1965-1998): d_out[16*i + k], k < count, each equal to what havoc_mi355x_satd returns for that pair. */
+ * turing/Search.hpp:1965-1998): d_out[16*i + k], k < count, each equal to what havoc_mi355x_satd returns for that pair.
+ * A count outside 1..16 is clamped: with count <= 0 nothing is written for the job, a count above 16 acts as 16; the
+ * entries d_out[16*i + k], k >= count, are never written, and the b_off slots past count must still hold offsets inside d_b. */
 int havoc_mi355x_satd_multi(havoc_mi355x_ctx *ctx, int S, int max_w, int max_h, const void *d_a, intptr_t stride_a,
                             const void *d_b, intptr_t stride_b, const havoc_mi355x_satd_multi_job *d_jobs, int njobs,
                             int32_t *d_out);
