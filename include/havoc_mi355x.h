@@ -1323,6 +1323,55 @@ typedef struct {
 int havoc_mi355x_temporal_candidates(havoc_mi355x_ctx *ctx, const havoc_mi355x_temporal_params *params, const havoc_mi355x_col_cell *d_store, intptr_t store_stride,
                                      const void *d_pus, int n, havoc_mi355x_temporal_cand *d_out);
 
+/* ---- the merge candidate lists of a committed picture's final coding units (csrc/kernels_merge.hip: k_cqt_merge_lists) ----
+ * For every final coding unit of the picture havoc_mi355x_cqt_commit left, the merge candidate list the reference derives for that unit (turing/Mvp.h:486-716; HEVC
+ * 8.5.3.2.2 - 8.5.3.2.5), and the lowest merge index whose candidate IS the unit's committed motion.  The rule is deriveMergeCandidateList of
+ * turingcodec_amd/search/merge_list.hpp, fetched by cqtMergeList of the same file -- one text compiled into the kernel and into the host clients.
+ * d_cqt_cells: havoc_mi355x_cqt_commit's map, (pic_height >> min_cb_log2) dense rows of (pic_width >> min_cb_log2).  d_pus: havoc_picture_pu[n]
+ * (turingcodec_amd/search/search_abi.h; x0, y0, w, h are read, nothing else); index p means the unit the cells call `unit == p`.  d_temporal:
+ * havoc_mi355x_temporal_cand[2 * n], index 2 * unit + list, as havoc_mi355x_temporal_candidates wrote it for the same d_pus, or NULL: no temporal candidate
+ * (slice_temporal_mvp_enabled_flag 0).  d_out[p] is unit p's record.
+ * Unit p = (x0, y0, w, h) is FINAL exactly when w == h == 1 << L with min_cb_log2 <= L <= ctb_log2, x0 >= 0, y0 >= 0, x0 + w <= pic_width, y0 + h <= pic_height, x0 and
+ * y0 are multiples of w, and the committed cell at (x0, y0) has unit == p and log2_size == L.  A final unit is one inter 2Nx2N prediction unit (partIdx 0).
+ * Its five neighbour positions, in list order: A1 (x0 - 1, y0 + h - 1), B1 (x0 + w - 1, y0 - 1), B0 (x0 + w, y0 - 1), A0 (x0 - 1, y0 + h), B2 (x0 - 1, y0 - 1).  A
+ * position gives a neighbour only when neighbourPositionAvailable (turingcodec_amd/search/picture_order.hpp: the picture's edges, a CTU that does not precede this
+ * one, the next CTU row, z-order inside the CTU) allows it AND the committed cell there has unit >= 0; no cell is read otherwise, never one outside the map.  A
+ * neighbour -- and the unit's own motion, from its origin cell -- is pred_flag[0] = pred != 1, pred_flag[1] = pred != 0, ref_idx 0, mv[l] of a used list, 0, 0 for
+ * an unused one.  The temporal candidate is available when either of the unit's two records is: pred_flag[l] = available_l, ref_idx 0, that record's vector (0, 0
+ * for a list without).
+ * The list: a B slice, one active reference per list, picture order counts ref_poc[0] / ref_poc[1] (compared for equality only, by the combined candidates),
+ * Log2ParMrgLevel 2, max_cand 1..5 (MaxNumMergeCand): spatial candidates pruned as the standard names the pairs, B2 only while fewer than four were taken, the temporal
+ * candidate, combined bi-predictive candidates, zero candidates.  (The 8x4 / 4x8 restriction cannot apply: the smallest unit is 8x8.)
+ * A final unit's record: n_cand = max_cand; cand[0 .. max_cand - 1] the list, the rest zero bytes; n_real = the candidates that are not zero candidates (the
+ * derivation's return value); match = the lowest k < n_cand whose candidate equals the unit's own motion -- per list the same pred_flag and, where used, the same
+ * ref_idx and vector (PuData::operator==) -- or -1.  Any other unit: an all-zero record with match = -1.  Every record is written once, as eight aligned 8-byte
+ * stores; nothing outside d_out[0 .. n - 1] is written.
+ * Argument order: ctx, params, d_cqt_cells (in), d_pus (in), n, d_temporal (in, or NULL), d_out (out).
+ * The inputs are trusted and never written.  EINVAL: a null pointer other than d_temporal; n < 0; ctb_log2 outside 4..6; min_cb_log2 outside 3..ctb_log2; a pic_width
+ * or pic_height that is not a positive multiple of 1 << min_cb_log2; max_cand outside 1..5; a non-zero reserved word; a pointer that is not 8-byte aligned; d_out
+ * equal to an input.  n == 0: returns 0 without a launch.
+ * One launch; no allocation, no synchronisation, no workspace: capturable into a HIP graph. */
+typedef struct {
+    int16_t mv[2][2];       /* [list][x, y], quarter samples; a list the candidate does not use: 0, 0 */
+    uint8_t pred_flag[2];
+    int8_t ref_idx[2];      /* 0 */
+} havoc_mi355x_merge_cand;          /* sizeof: 12 */
+typedef struct {
+    havoc_mi355x_merge_cand cand[5];
+    int8_t n_cand;          /* max_cand for a final unit, else 0 */
+    int8_t n_real;          /* how many of them are not zero candidates */
+    int8_t match;           /* the lowest merge index that carries the unit's committed motion; -1: none */
+    uint8_t reserved;       /* 0 */
+} havoc_mi355x_merge_list;          /* sizeof: 64 */
+typedef struct {
+    int32_t pic_width, pic_height, ctb_log2, min_cb_log2;
+    int32_t max_cand;               /* 1..5 */
+    int32_t ref_poc[2];             /* picture order counts of RefPicList0[0] / RefPicList1[0] */
+    int32_t reserved[5];            /* 0 */
+} havoc_mi355x_merge_params;        /* sizeof: 48 */
+int havoc_mi355x_cqt_merge_lists(havoc_mi355x_ctx *ctx, const havoc_mi355x_merge_params *params, const havoc_mi355x_cqt_cell *d_cqt_cells, const void *d_pus, int n,
+                                 const havoc_mi355x_temporal_cand *d_temporal, havoc_mi355x_merge_list *d_out);
+
 /* ---- an intra picture's partitions with their real dependencies (round 4; csrc/kernels_decide.hip) ----
  * A partition predicts from the reconstruction of what precedes it (turing/Reconstruct.cpp:609-615) and takes candModeList from its neighbours' decided modes
  * (turing/CandModeList.h:33-95).  A client that runs the batch chain over the partitions level by level (every partition of a level has all its neighbours final)

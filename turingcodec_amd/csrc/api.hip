@@ -38,6 +38,8 @@ static_assert(sizeof(havoc_mi355x_cqt_ctu) == 40 && offsetof(havoc_mi355x_cqt_ct
 static_assert(sizeof(havoc_mi355x_cqt_cell) == 24 && offsetof(havoc_mi355x_cqt_cell, mv) == 8 && offsetof(havoc_mi355x_cqt_cell, log2_size) == 16 &&
               offsetof(havoc_mi355x_cqt_cell, cbf) == 20 && sizeof(havoc_mi355x_cqt_commit_args) == 288 && offsetof(havoc_mi355x_cqt_commit_args, d_units) == 24 &&
               offsetof(havoc_mi355x_cqt_commit_args, luma_pieces) == 104 && offsetof(havoc_mi355x_cqt_commit_args, d_rec_y) == 224, "the quadtree commit records are ABI");
+static_assert(sizeof(havoc_mi355x_merge_cand) == 12 && sizeof(havoc_mi355x_merge_list) == 64 && offsetof(havoc_mi355x_merge_list, n_cand) == 60 &&
+              sizeof(havoc_mi355x_merge_params) == 48 && offsetof(havoc_mi355x_merge_params, ref_poc) == 20, "the merge list records are ABI");
 static_assert(sizeof(havoc_mi355x_intra_rate_job) == 32 && offsetof(havoc_mi355x_intra_rate_job, scan_idx) == 12 && offsetof(havoc_mi355x_intra_rate_job, flags) == 15,
               "job ABI");
 static_assert(sizeof(havoc_mi355x_pred_select_job) == 32 && offsetof(havoc_mi355x_pred_select_job, log2_size) == 24, "job ABI");
@@ -1337,6 +1339,30 @@ int havoc_mi355x_temporal_candidates(havoc_mi355x_ctx *ctx, const havoc_mi355x_t
             "temporal_candidates: the destination must not be an input (which is never written)");
     if (n == 0) return 0;
     return check(launch_temporal_candidates(LS(ctx), *params, d_store, (long)store_stride, d_pus, n, d_out), "temporal_candidates");
+}
+
+int havoc_mi355x_cqt_merge_lists(havoc_mi355x_ctx *ctx, const havoc_mi355x_merge_params *params, const havoc_mi355x_cqt_cell *d_cqt_cells, const void *d_pus, int n,
+                                 const havoc_mi355x_temporal_cand *d_temporal, havoc_mi355x_merge_list *d_out)
+{
+    REQUIRE_CTX();
+    REQUIRE(params != nullptr, "cqt_merge_lists: null params");
+    REQUIRE(d_cqt_cells != nullptr && d_pus != nullptr && d_out != nullptr, "cqt_merge_lists: null device pointer");
+    REQUIRE(n >= 0 && n < (1 << 25), "cqt_merge_lists: n must be 0 .. 2^25 - 1");
+    REQUIRE(params->ctb_log2 >= 4 && params->ctb_log2 <= 6, "cqt_merge_lists: ctb_log2 must be 4..6");
+    REQUIRE(params->min_cb_log2 >= 3 && params->min_cb_log2 <= params->ctb_log2, "cqt_merge_lists: min_cb_log2 must be 3..ctb_log2");
+    REQUIRE(params->pic_width > 0 && params->pic_height > 0 && params->pic_width % (1 << params->min_cb_log2) == 0 && params->pic_height % (1 << params->min_cb_log2) == 0,
+            "cqt_merge_lists: pic_width and pic_height must be positive multiples of the minimum coding block size");
+    REQUIRE(params->max_cand >= 1 && params->max_cand <= 5, "cqt_merge_lists: max_cand must be 1..5");
+    for (int r : params->reserved)
+        REQUIRE(r == 0, "cqt_merge_lists: reserved words must be 0");
+    REQUIRE((reinterpret_cast<uintptr_t>(d_cqt_cells) & 7) == 0 && (reinterpret_cast<uintptr_t>(d_pus) & 7) == 0 && (reinterpret_cast<uintptr_t>(d_temporal) & 7) == 0 &&
+                (reinterpret_cast<uintptr_t>(d_out) & 7) == 0,
+            "cqt_merge_lists: d_cqt_cells, d_pus, d_temporal and d_out must be 8-byte aligned");
+    REQUIRE(static_cast<const void *>(d_out) != static_cast<const void *>(d_cqt_cells) && static_cast<const void *>(d_out) != d_pus &&
+                static_cast<const void *>(d_out) != static_cast<const void *>(d_temporal),
+            "cqt_merge_lists: the destination must not be an input (which is never written)");
+    if (n == 0) return 0;
+    return check(launch_cqt_merge_lists(LS(ctx), *params, d_cqt_cells, d_pus, n, d_temporal, d_out), "cqt_merge_lists");
 }
 
 } // extern "C"

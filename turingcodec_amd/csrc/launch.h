@@ -67,6 +67,8 @@ hipError_t launch_cqt_block_cells(hipStream_t, int width, int height, int minCbL
 hipError_t launch_cqt_motion_store(hipStream_t, int width, int height, int minCbLog2, int refPoc0, int refPoc1, const havoc_mi355x_cqt_cell *, havoc_mi355x_col_cell *);
 hipError_t launch_temporal_candidates(hipStream_t, const havoc_mi355x_temporal_params &, const havoc_mi355x_col_cell *, long stride, const void *pus, int n,
                                       havoc_mi355x_temporal_cand *);
+hipError_t launch_cqt_merge_lists(hipStream_t, const havoc_mi355x_merge_params &, const havoc_mi355x_cqt_cell *, const void *pus, int n,
+                                  const havoc_mi355x_temporal_cand *temporal, havoc_mi355x_merge_list *);
 hipError_t launch_intra_order(hipStream_t, const int32_t *, const havoc_mi355x_intra_mpm *, int, int32_t, int32_t *, int32_t *, int32_t *, int32_t *);
 hipError_t launch_intra_expand(hipStream_t, const havoc_mi355x_intra_search_job *, const int32_t *, const int32_t *, const int32_t *, const int32_t *, int, int, int, int, int,
                                int, int, int, havoc_mi355x_intra_job *, havoc_mi355x_tu_fused_job *, havoc_mi355x_rdoq_job *, int32_t *, int32_t *);

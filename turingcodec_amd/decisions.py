@@ -463,8 +463,12 @@ class DecisionPicture:
 
     def __init__(self, hv, width, height, bit_depth=8, qp=32, seed=11, threads=16, frames=None, density=1.0, intra=True, search_on_device=True, distance=1,
                  sao=False, residual_rates=False, tree_rates=False, pu_modes=False, cu_close=False, cqt=False, unit_trees=False, commit=False, finish=False,
-                 motion=None, col=None, temporal_mvp=False):
-        """motion=(poc, ref_poc0, ref_poc1) (needs commit=True): the committed picture also leaves its collocated motion store in `cqt_store`
+                 motion=None, col=None, temporal_mvp=False, merge_lists=None):
+        """merge_lists=max_cand (1..5; needs commit=True and motion=, whose two references are the lists' picture order counts): the merge candidate list of every
+        final coding unit of the committed picture and the lowest merge index that carries the unit's committed motion, into `cqt_merge` (havoc.MERGE_LIST_DT per
+        searched unit; havoc_mi355x_cqt_merge_lists, behind the commit -- and behind the temporal candidates -- inside the replayed graph; cqt_merge_results()).  With
+        col= the lists take that option's temporal records (col["target_poc"] must be motion's two references); without col= they have no temporal candidate.
+        motion=(poc, ref_poc0, ref_poc1) (needs commit=True): the committed picture also leaves its collocated motion store in `cqt_store`
         (havoc_mi355x_cqt_motion_store, directly behind the commit inside the replayed graph; cqt_motion_results()) -- with finish=True the two things a reference
         picture is.
         col=dict(store=<device tensor of havoc.COL_CELL_DT records, dense rows: another picture's cqt_store>, col_poc=, cur_poc=, target_poc=(l0, l1), all_backwards=,
@@ -477,8 +481,15 @@ class DecisionPicture:
         the table on the context for the search and removes it afterwards -- also when the search raises; temporal_candidates() returns the records as before.  What
         follows the searches (pu_candidates, pu_rate, cu_close, cqt, the commit, the motion store) reads their results in place and needs nothing of its own."""
         import torch
+        if merge_lists is not None and (not commit or motion is None):
+            raise ValueError("merge_lists=max_cand derives the committed picture's merge candidate lists: it needs commit=True and motion=(poc, ref_poc0, ref_poc1)")
         if motion is not None and not commit:
             raise ValueError("motion=(poc, ref_poc0, ref_poc1) makes the collocated motion store of the committed picture: it needs commit=True")
+        if merge_lists is not None:
+            if isinstance(merge_lists, bool) or int(merge_lists) != merge_lists or not 1 <= int(merge_lists) <= 5:
+                raise ValueError("merge_lists must be the number of merge candidates, 1..5")
+            if col is not None and "target_poc" in col and tuple(int(v) for v in col["target_poc"]) != tuple(int(v) for v in tuple(motion)[1:3]):
+                raise ValueError("merge_lists: col['target_poc'] differs from motion's two references (the temporal candidates were scaled towards other pictures)")
         if col is not None and not search_on_device:
             raise ValueError("col= needs the device route (search_on_device=True)")
         if temporal_mvp and col is None:
@@ -541,6 +552,8 @@ class DecisionPicture:
         # this picture's own temporal candidates from ANOTHER picture's store (havoc_mi355x_temporal_candidates): the caller's dict or None
         self.col = None if col is None else dict(col)
         self.temporal_mvp = bool(temporal_mvp)      # ... consumed by the search walk's predictor derivation (havoc_mi355x_search_temporal)
+        # the committed picture's merge candidate lists (havoc_mi355x_cqt_merge_lists): MaxNumMergeCand or None
+        self.merge_lists = None if merge_lists is None else int(merge_lists)
         self.sao = sao                               # in-loop SAO between deblocking and padding (sao_filter_inputs / sao_loop_filter)
         from . import havoc as hmod
         from . import workload
@@ -650,6 +663,10 @@ class DecisionPicture:
                                                          c["collocated_from_l0"])
             self._d_temporal_pus = hv.up(np.ascontiguousarray(self.pus).view(np.uint8).reshape(-1))
             self._d_temporal = hv.zeros(max(1, 2 * len(self.pus)) * hmod.TEMPORAL_CAND_DT.itemsize, np.uint8)
+        if self.merge_lists is not None:    # a record per searched unit; the units' table as the temporal candidates read it (shared with col= where both are given)
+            self._merge_params = hmod.merge_params(width, height, self.CQT_CTB_LOG2, self.CQT_MIN_CB_LOG2, self.merge_lists, self.motion[1:3])
+            self._d_merge_pus = self._d_temporal_pus if self.col is not None else hv.up(np.ascontiguousarray(self.pus).view(np.uint8).reshape(-1))
+            self.cqt_merge = hv.zeros(max(1, len(self.pus)) * hmod.MERGE_LIST_DT.itemsize, np.uint8)
         # ---- the intra candidates of the picture (an inter picture evaluates them per coding unit): partitions with neighbours from the source
         self.intra_parts = {}
         self.rsl = float(self.params.reciprocal_sqrt_lambda)
@@ -1110,6 +1127,22 @@ class DecisionPicture:
             n = len(self.pus)
             self._temporal = self.hv.down(self._d_temporal, np.uint8)[:2 * n * self.hmod.TEMPORAL_CAND_DT.itemsize].view(self.hmod.TEMPORAL_CAND_DT).reshape(n, 2).copy()
         return self._temporal
+
+    # ---- the committed picture's merge candidate lists (turing/Mvp.h:486-716) -----------------------------------------------------------------------------------
+    def cqt_merge_launch(self):
+        """behind cqt_commit_launch and, with col=, behind temporal_launch: the merge candidate list of every final coding unit from cqt_cells (the neighbours in their
+        final state) and this picture's temporal records, into cqt_merge.  One launch; asynchronous"""
+        self.hv.cqt_merge_lists_d(self._merge_params, self.cqt_cells, self._d_merge_pus, len(self.pus), self._d_temporal if self.col is not None else None,
+                                  self.cqt_merge)
+
+    def cqt_merge_results(self):
+        """what cqt_merge_launch() left on the device, as numpy: havoc.MERGE_LIST_DT [len(self.pus)] -- a final unit's list, n_real and match; any other unit: zero
+        bytes with match -1"""
+        if self.merge_lists is None:
+            raise ValueError("cqt_merge_results: the picture was made without merge_lists=max_cand")
+        if getattr(self, "_cqt_merge", None) is None:
+            self._cqt_merge = self.hv.cqt_merge_lists_download(self.cqt_merge, len(self.pus))
+        return self._cqt_merge
 
     # ---- the committed picture finished: block structure, boundary strengths, deblocking, padding (turing/TaskDeblock.cpp:105-167) --------------------------------
     def cqt_finish_launch(self):
@@ -1814,7 +1847,7 @@ class DecisionPicture:
             # everything after the searches is a FIXED sequence of launches over device-resident tables (the decided field never leaves the device, the decisions
             # between the launches are kernels): recorded once into a HIP graph, one launch per picture, one wait at the end
             self._rqt = self._cells = self._sao_decisions = self._rqt_rates = self._rqt_tree = self._cu_decisions = self._cqt_decisions = None
-            self._unit_tree_decisions = self._cqt_commit = self._cqt_finish = self._cqt_motion = self._temporal = None
+            self._unit_tree_decisions = self._cqt_commit = self._cqt_finish = self._cqt_motion = self._temporal = self._cqt_merge = None
             pu = (self.pu_mode_launches,) if self.pu_modes else ()      # (the tables its launches read went up before the replay: pu_candidates)
             pu += (self.unit_tree_launches,) if self.unit_trees else ()  # (behind pu_decide: it reads the winners in place; before cu_close, which reads its records)
             pu += (self.cu_close_launches,) if self.cu_close else ()     # (after the tree decisions AND the prediction units' rates: it reads both in place)
@@ -1824,6 +1857,7 @@ class DecisionPicture:
             pu += (self.cqt_finish_launch,) if self.finish else ()       # (behind the commit: it filters and pads what that wrote, in place)
             pu += (self.temporal_launch,) if self.col is not None and not self.temporal_mvp else ()      # (reads another picture's store and this picture's unit table
                                                                                                          # only; with temporal_mvp it ran before the searches)
+            pu += (self.cqt_merge_launch,) if self.merge_lists is not None else ()      # (behind the commit, whose cells it reads, and the temporal candidates)
             if self.sao:
                 self._replayed("after the searches", lambda: (self.merge_candidates(field), self.predict(field), self.sao_filter_inputs(field),
                                                               self.sao_loop_filter(), [f() for f in pu]))

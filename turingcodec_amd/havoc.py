@@ -142,6 +142,7 @@ def _load():
         "cqt_block_cells": [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _ip],
         "cqt_motion_store": [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
         "temporal_candidates": [_vp, _vp, _vp, _ip, _vp, _i, _vp],
+        "cqt_merge_lists": [_vp, _vp, _vp, _vp, _i, _vp, _vp],
         "intra_decide_rated": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_int32, _vp, _vp],
         "rqt_decide_rated": [_vp, _vp, _i, _vp, _vp, _vp, _vp, C.c_int64, C.c_ssize_t, _i, _i, _vp],
         "rqt_decide_tree": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_ssize_t, _i, C.c_int64, C.c_int64, C.c_ssize_t, _i, _i, _vp, _vp],
@@ -376,6 +377,22 @@ TEMPORAL_PARAMS_DT = np.dtype([("pic_width", "<i4"), ("pic_height", "<i4"), ("ct
 TEMPORAL_CAND_DT = np.dtype([("mv", "<i2", (2,)), ("available", "<i2"), ("source", "<i2")])
 assert COL_CELL_DT.itemsize == 24 and TEMPORAL_PARAMS_DT.itemsize == 48 and TEMPORAL_CAND_DT.itemsize == 8
 TEMPORAL_NONE, TEMPORAL_BOTTOM_RIGHT, TEMPORAL_CENTRE = 0, 1, 2
+
+
+# one havoc_mi355x_merge_cand, 12 bytes; one havoc_mi355x_merge_list, 64 bytes: a final coding unit's merge candidate list (n_cand places of cand are the list,
+# n_real of them are not zero candidates, match: the lowest merge index that carries the unit's committed motion or -1); one havoc_mi355x_merge_params, 48 bytes
+MERGE_CAND_DT = np.dtype([("mv", "<i2", (2, 2)), ("pred_flag", "u1", (2,)), ("ref_idx", "i1", (2,))])
+MERGE_LIST_DT = np.dtype([("cand", MERGE_CAND_DT, (5,)), ("n_cand", "i1"), ("n_real", "i1"), ("match", "i1"), ("reserved", "u1")])
+MERGE_PARAMS_DT = np.dtype([("pic_width", "<i4"), ("pic_height", "<i4"), ("ctb_log2", "<i4"), ("min_cb_log2", "<i4"), ("max_cand", "<i4"), ("ref_poc", "<i4", (2,)),
+                            ("reserved", "<i4", (5,))])
+assert MERGE_CAND_DT.itemsize == 12 and MERGE_LIST_DT.itemsize == 64 and MERGE_PARAMS_DT.itemsize == 48
+
+
+def merge_params(pic_width, pic_height, ctb_log2, min_cb_log2, max_cand, ref_poc):
+    """-> one MERGE_PARAMS_DT record"""
+    p = np.zeros(1, MERGE_PARAMS_DT)
+    p["pic_width"], p["pic_height"], p["ctb_log2"], p["min_cb_log2"], p["max_cand"], p["ref_poc"] = pic_width, pic_height, ctb_log2, min_cb_log2, max_cand, tuple(ref_poc)
+    return p
 
 
 def temporal_params(pic_width, pic_height, ctb_log2, col_poc, cur_poc, target_poc, all_backwards, collocated_from_l0):
@@ -1219,6 +1236,18 @@ class Havoc:
         [2 n], index 2 * pu + list.  No sync."""
         params = np.ascontiguousarray(params, TEMPORAL_PARAMS_DT).reshape(1)
         self._ck(self.L.havoc_mi355x_temporal_candidates(self.h, params.ctypes.data, _ptr(store), int(store_stride), _ptr(pus), int(n), _ptr(out)))
+
+    def cqt_merge_lists_d(self, params, cqt_cells, pus, n, temporal, out):
+        """the merge candidate list of every final coding unit of a committed picture (havoc_mi355x_cqt_merge_lists): params: one MERGE_PARAMS_DT record (read during
+        the call); cqt_cells: cqt_commit_d's cell map; pus: uint8 tensor of workload.PICTURE_PU_DT [n]; temporal: uint8 tensor of TEMPORAL_CAND_DT [2 * n] as
+        temporal_candidates_d wrote it for the same units, or None (no temporal candidate); out: uint8 tensor of MERGE_LIST_DT [n], every record written.  No sync."""
+        params = np.ascontiguousarray(params, MERGE_PARAMS_DT).reshape(1)
+        self._ck(self.L.havoc_mi355x_cqt_merge_lists(self.h, params.ctypes.data, _ptr(cqt_cells), _ptr(pus), int(n), None if temporal is None else _ptr(temporal),
+                                                     _ptr(out)))
+
+    def cqt_merge_lists_download(self, out, n):
+        """cqt_merge_lists_d's records as numpy: MERGE_LIST_DT [n]"""
+        return self.down(out, np.uint8)[:n * MERGE_LIST_DT.itemsize].view(MERGE_LIST_DT).copy()
 
     def unit_pred_ssd_d(self, bit_depth, src_y, src_stride, src_c, src_stride_c, pred_y, pred_stride, pred_c, pred_stride_c, jobs, out):
         """SSD(source, prediction) of units' luma, Cb and Cr blocks in one launch (havoc_mi355x_unit_pred_ssd); jobs: uint8 tensor of PRED_SSD_JOB_DT; out: int32 [3 n].
