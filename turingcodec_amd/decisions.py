@@ -6,9 +6,11 @@ Plain ctypes over raw device pointers and a havoc_mi355x context handle, so that
 """
 import ctypes as C
 import os
+import typing
 
 import numpy as np
 
+from . import tu_plan
 from .workload import PICTURE_PU_DT
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -59,13 +61,7 @@ class RqtStats(C.Structure):
 
 def rqt_quant(qp, bit_depth):
     """havoc_rqt_quant[4] for transform sizes 4..32 of an inter (non-I slice) luma block (turing/QpState.h:85-94, Reconstruct.cpp:774-782)"""
-    from . import workload
-    q = np.zeros((4, 4), np.int32)
-    for log2 in (2, 3, 4, 5):
-        qs, qshift, _ = workload.quant_params(qp, log2, bit_depth, False)
-        inv, dshift = workload.dequant_params(qp, log2, bit_depth)
-        q[log2 - 2] = (qs, qshift, inv, dshift)
-    return q
+    return np.array([tu_plan.quantiser(qp, bit_depth, log2) for log2 in (2, 3, 4, 5)], np.int32)
 
 
 def medium_params(width, height, bit_depth, reciprocal_sqrt_lambda, concurrent_frames=4):
@@ -430,6 +426,94 @@ def rqt_units(width, height, ctus_x):
     return np.array(rows, np.int32).reshape(-1, 4).view(RQT_CU_DT).reshape(-1)
 
 
+class Stage(typing.NamedTuple):
+    """one stage of DecisionPicture's step behind the transform trees and the loop filter, inside the replayed sequence"""
+    option: str              # the constructor option that enables it (on unless False / None); the picture keeps it as an attribute of the same name
+    launch: str              # the method that issues its launches
+    requires: tuple          # ((violated(o), message), ...) over the constructor's options o, in the order they are checked
+    banded: str = None       # why step_banded refuses it (None: what it requires is refused already)
+    extra: str = None        # results(): the getter of what it decided (None: it has a results method of its own)
+
+
+def _off_device(o):
+    return not o["search_on_device"]
+
+
+def _no_8_grid(o):
+    return bool(o["width"] % 8 or o["height"] % 8)
+
+
+def _merge_lists_count(o):
+    m = o["merge_lists"]
+    return isinstance(m, bool) or int(m) != m or not 1 <= int(m) <= 5
+
+
+def _merge_lists_targets(o):
+    col = o["col"]
+    return col is not None and "target_poc" in col and tuple(int(v) for v in col["target_poc"]) != tuple(int(v) for v in tuple(o["motion"])[1:3])
+
+
+# in step()'s order: every stage reads in place what the stages before it left on the device
+STAGES = (
+    # (the tables its launches read went up before the replay: pu_candidates)
+    Stage("pu_modes", "pu_mode_launches", ((_off_device, "pu_modes=True needs the device route (search_on_device=True)"),),
+          banded="step_banded does not decide the prediction units' modes: use step() with pu_modes=True", extra="pu_decisions"),
+    # (behind pu_decide: it reads the winners in place; before cu_close, which reads its records)
+    Stage("unit_trees", "unit_tree_launches",
+          ((_off_device, "unit_trees=True needs the device route (search_on_device=True)"),
+           (lambda o: not (o["tree_rates"] and o["pu_modes"] and o["cu_close"]),
+            "unit_trees=True gives every searched unit the tree of its winning prediction and closes it: it needs tree_rates=True, pu_modes=True and cu_close=True"),
+           (_no_8_grid, "unit_trees=True needs a width and a height that are multiples of 8 (the unit prediction planes are addressed in 8-byte pieces)")),
+          banded="step_banded does not build the searched units' trees: use step() with unit_trees=True", extra="unit_tree_decisions"),
+    # (after the tree decisions AND the prediction units' rates: it reads both in place)
+    Stage("cu_close", "cu_close_launches",
+          ((_off_device, "cu_close=True needs the device route (search_on_device=True)"),
+           (lambda o: not (o["tree_rates"] and o["pu_modes"]),
+            "cu_close=True closes a unit over its tree's and its prediction unit's CABAC bits: it needs tree_rates=True and pu_modes=True")),
+          banded="step_banded does not close coding units: use step() with cu_close=True", extra="cu_decisions"),
+    # (behind cu_close: it reads its records in place)
+    Stage("cqt", "cqt_launch",
+          ((_off_device, "cqt=True needs the device route (search_on_device=True)"),
+           (lambda o: not o["cu_close"], "cqt=True decides the coding quadtree over closed coding units: it needs cu_close=True"),
+           (_no_8_grid, "cqt=True needs a width and a height that are multiples of the minimum coding block size, 8")),
+          banded="step_banded does not decide coding quadtrees: use step() with cqt=True", extra="cqt_decisions"),
+    # (directly behind the quadtree: it acts on its records, into buffers of its own)
+    Stage("commit", "cqt_commit_launch",
+          ((lambda o: not (o["unit_trees"] and o["cqt"]),
+            "commit=True commits the quadtree decided over the searched units into one picture: it needs unit_trees=True and cqt=True"),)),
+    # (directly behind the commit: it reads the cells that wrote, nothing else)
+    Stage("motion", "cqt_motion_launch",
+          ((lambda o: not o["commit"], "motion=(poc, ref_poc0, ref_poc1) makes the collocated motion store of the committed picture: it needs commit=True"),)),
+    # (behind the commit: it filters and pads what that wrote, in place)
+    Stage("finish", "cqt_finish_launch", ((lambda o: not o["commit"], "finish=True deblocks and pads the committed picture: it needs commit=True"),)),
+    # (reads another picture's store and this picture's unit table only; with temporal_mvp step() issues it BEFORE the searches instead, outside the replay)
+    Stage("col", "temporal_launch", ((_off_device, "col= needs the device route (search_on_device=True)"),),
+          banded="step_banded does not derive temporal candidates: use step() with col="),
+    # (behind the commit, whose cells it reads, and the temporal candidates)
+    Stage("merge_lists", "cqt_merge_launch",
+          ((lambda o: not o["commit"] or o["motion"] is None,
+            "merge_lists=max_cand derives the committed picture's merge candidate lists: it needs commit=True and motion=(poc, ref_poc0, ref_poc1)"),
+           (_merge_lists_count, "merge_lists must be the number of merge candidates, 1..5"),
+           (_merge_lists_targets, "merge_lists: col['target_poc'] differs from motion's two references (the temporal candidates were scaled towards other pictures)"))),
+)
+# the options that change the step's route without being a stage of their own
+ROUTE_REQUIRES = {
+    "temporal_mvp": ((lambda o: o["col"] is None, "temporal_mvp=True feeds the temporal candidates of col= into the search walk's predictors: it needs col="),),
+    "sao": ((_off_device, "sao=True needs the device route (search_on_device=True)"),),
+    "residual_rates": ((_off_device, "residual_rates=True needs the device route (search_on_device=True)"),),
+    "tree_rates": ((_off_device, "tree_rates=True needs the device route (search_on_device=True)"),
+                   (lambda o: o["residual_rates"], "tree_rates=True prices the whole transform tree, residuals included: not together with residual_rates=True"),
+                   (lambda o: o["sao"], "tree_rates=True together with sao=True is not built")),
+}
+# the order the constructor has always made its refusals in: a caller with two mistakes sees the same one
+CHECK_ORDER = ("merge_lists", "motion", "col", "temporal_mvp", "finish", "commit", "unit_trees", "cqt", "cu_close", "pu_modes", "sao", "residual_rates", "tree_rates")
+
+
+def _on(option, value):
+    """motion=, col= and merge_lists= carry a value (on unless None); every other option is a flag"""
+    return value is not None if option in ("motion", "col", "merge_lists") else bool(value)
+
+
 class DecisionPicture:
     """One inter picture through the DECISION-DRIVEN path on the device (bench.py --decisions, tests/test_decisions.py):
 
@@ -450,6 +534,11 @@ class DecisionPicture:
 
     What is NOT in it (stated, not hidden): the encoder's mode decision between the searched PUs (every PU of workload.picture_pus is
     searched and the last one covering an area stands) and between inter and intra, bi-prediction, CABAC.  `step()` is what bench.py times.
+
+    How it is put together: the formats of the transform chains -- RDOQ job records, where a unit's candidates lie, tree-rate jobs -- are tu_plan.py's; _chain_group
+    gives a job table its buffers, _chain / _chain_final issue a chain over groups, _tree_tables builds rqt_plan (self.units) and unit_plan (self.pus) alike.  The stages
+    behind the trees (pu_modes ... merge_lists) are the rows of STAGES: the constructor's refusals, step()'s sequence, step_banded's refusals and results()' extras
+    are read from it -- a new stage is one row and its own methods.  What the getters download is kept in one cache until the next step (_forget).
 
     pu_modes=True (device route only) adds the decision WITHIN every searched prediction unit that go2 takes (turing/Search.hpp:1844-1902): its uni L0, uni L1 and
     bi candidates -- the search's own records: the two uni-directional results and the two bi-directional refinements, list l's refined record holding what
@@ -481,52 +570,15 @@ class DecisionPicture:
         the table on the context for the search and removes it afterwards -- also when the search raises; temporal_candidates() returns the records as before.  What
         follows the searches (pu_candidates, pu_rate, cu_close, cqt, the commit, the motion store) reads their results in place and needs nothing of its own."""
         import torch
-        if merge_lists is not None and (not commit or motion is None):
-            raise ValueError("merge_lists=max_cand derives the committed picture's merge candidate lists: it needs commit=True and motion=(poc, ref_poc0, ref_poc1)")
-        if motion is not None and not commit:
-            raise ValueError("motion=(poc, ref_poc0, ref_poc1) makes the collocated motion store of the committed picture: it needs commit=True")
-        if merge_lists is not None:
-            if isinstance(merge_lists, bool) or int(merge_lists) != merge_lists or not 1 <= int(merge_lists) <= 5:
-                raise ValueError("merge_lists must be the number of merge candidates, 1..5")
-            if col is not None and "target_poc" in col and tuple(int(v) for v in col["target_poc"]) != tuple(int(v) for v in tuple(motion)[1:3]):
-                raise ValueError("merge_lists: col['target_poc'] differs from motion's two references (the temporal candidates were scaled towards other pictures)")
-        if col is not None and not search_on_device:
-            raise ValueError("col= needs the device route (search_on_device=True)")
-        if temporal_mvp and col is None:
-            raise ValueError("temporal_mvp=True feeds the temporal candidates of col= into the search walk's predictors: it needs col=")
-        if finish and not commit:
-            raise ValueError("finish=True deblocks and pads the committed picture: it needs commit=True")
-        if commit and not (unit_trees and cqt):
-            raise ValueError("commit=True commits the quadtree decided over the searched units into one picture: it needs unit_trees=True and cqt=True")
-        if unit_trees and not search_on_device:
-            raise ValueError("unit_trees=True needs the device route (search_on_device=True)")
-        if unit_trees and not (tree_rates and pu_modes and cu_close):
-            raise ValueError("unit_trees=True gives every searched unit the tree of its winning prediction and closes it: it needs tree_rates=True, pu_modes=True "
-                             "and cu_close=True")
-        if unit_trees and (width % 8 or height % 8):
-            raise ValueError("unit_trees=True needs a width and a height that are multiples of 8 (the unit prediction planes are addressed in 8-byte pieces)")
-        if cqt and not search_on_device:
-            raise ValueError("cqt=True needs the device route (search_on_device=True)")
-        if cqt and not cu_close:
-            raise ValueError("cqt=True decides the coding quadtree over closed coding units: it needs cu_close=True")
-        if cqt and (width % 8 or height % 8):
-            raise ValueError("cqt=True needs a width and a height that are multiples of the minimum coding block size, 8")
-        if cu_close and not search_on_device:
-            raise ValueError("cu_close=True needs the device route (search_on_device=True)")
-        if cu_close and not (tree_rates and pu_modes):
-            raise ValueError("cu_close=True closes a unit over its tree's and its prediction unit's CABAC bits: it needs tree_rates=True and pu_modes=True")
-        if pu_modes and not search_on_device:
-            raise ValueError("pu_modes=True needs the device route (search_on_device=True)")
-        if sao and not search_on_device:
-            raise ValueError("sao=True needs the device route (search_on_device=True)")
-        if residual_rates and not search_on_device:
-            raise ValueError("residual_rates=True needs the device route (search_on_device=True)")
-        if tree_rates and not search_on_device:
-            raise ValueError("tree_rates=True needs the device route (search_on_device=True)")
-        if tree_rates and residual_rates:
-            raise ValueError("tree_rates=True prices the whole transform tree, residuals included: not together with residual_rates=True")
-        if tree_rates and sao:
-            raise ValueError("tree_rates=True together with sao=True is not built")
+        o = dict(width=width, height=height, search_on_device=search_on_device, sao=sao, residual_rates=residual_rates, tree_rates=tree_rates, pu_modes=pu_modes,
+                 cu_close=cu_close, cqt=cqt, unit_trees=unit_trees, commit=commit, finish=finish, motion=motion, col=col, temporal_mvp=temporal_mvp,
+                 merge_lists=merge_lists)
+        requires = dict(ROUTE_REQUIRES, **{s.option: s.requires for s in STAGES})
+        for option in CHECK_ORDER:
+            if _on(option, o[option]):
+                for violated, message in requires[option]:
+                    if violated(o):
+                        raise ValueError(message)
         # the transform-tree decision prices each candidate's residual with the reference's CABAC bits (havoc_mi355x_residual_rate) in place of the stand-in
         self.residual_rates = residual_rates
         # ... or compares what the reference compares: the whole transform_tree's bits of both depths (havoc_mi355x_tree_rate) and the distortion of three planes
@@ -590,43 +642,18 @@ class DecisionPicture:
                 continue
             xs, ys = np.meshgrid(np.arange(0, width // nn * nn, nn), np.arange(y_lo, y_hi, nn))
             x0, y0 = xs.ravel().astype(np.int64), ys.ravel().astype(np.int64)
-            m = len(x0)
-            qs, qshift, _ = workload.quant_params(qp, log2, bit_depth, False)
-            inv, dshift = workload.dequant_params(qp, log2, bit_depth)
-            fj = np.zeros((m, 4), np.int32)
-            fj[:, 0] = np.arange(m) * nn * nn
-            fj[:, 1] = fj[:, 3] = (y0 + self.PAD) * self.stride + x0 + self.PAD
-            fj[:, 2] = y0 * width + x0
-            jobs = np.zeros(m, hmod.RDOQ_JOB_DT)
-            jobs["dst_off"] = jobs["src_off"] = fj[:, 0]
-            jobs["quant_scale"], jobs["quant_shift"], jobs["inv_scale"] = qs, qshift, inv
-            jobs["lambda_q16"], jobs["sdh_factor"] = hmod.rdoq_lambda(lam, inv)
-            jobs["sdh"] = 1
-            jobs["ctx_index"] = (y0 // 64) * self.cx + x0 // 64
-            with torch.cuda.stream(hv.tstream):
-                d_rj = torch.from_numpy(jobs.view(np.uint8).reshape(-1)).to(hv.device)
-            self.groups.append(dict(log2=log2, nn=nn, x0=x0, y0=y0, m=m, inv=inv, dshift=dshift, d_fj=hv.up(fj), d_rj=d_rj,
-                                    pj=np.zeros((m, 8), np.int32), d_pj=hv.zeros(m * 8, np.int32), coef=hv.zeros(m * nn * nn, np.int16),
-                                    level=hv.zeros(m * nn * nn, np.int16), cbf=hv.zeros(m, np.int32), ssd=hv.zeros(m, np.uint32),
-                                    work=hv.rdoq_workspace(m)))
-        srng = np.random.default_rng(seed + 7919)
-        base = srng.integers(4, 100, 128)
-        self.rdoq_states = np.clip(base[None, :] + srng.integers(-6, 7, (self.cx * self.cy, 128)), 0, 125).astype(np.uint8)
-        self.d_states = hv.up(self.rdoq_states.reshape(-1))
-        if tree_rates:      # the contexts outside the 128-byte snapshot (HAVOC_INTRA_SYNTAX_CTX_*: split_transform_flag's), per CTU, seeded the same way
-            yrng = np.random.default_rng(seed + 7927)
-            self.syntax_states = np.clip(yrng.integers(4, 100, 4)[None, :] + yrng.integers(-6, 7, (self.cx * self.cy, 4)), 0, 125).astype(np.uint8)
-            self.d_syntax_states = hv.up(self.syntax_states.reshape(-1))
-        if pu_modes:        # prediction_unit()'s contexts (HAVOC_PU_SYNTAX_CTX_*), per CTU, seeded the same way
-            prng = np.random.default_rng(seed + 7933)
-            self.pu_syntax_states = np.clip(prng.integers(4, 100, hmod.PU_SYNTAX_CTX_BYTES)[None, :] +
-                                            prng.integers(-6, 7, (self.cx * self.cy, hmod.PU_SYNTAX_CTX_BYTES)), 0, 125).astype(np.uint8)
-            self.d_pu_syntax_states = hv.up(self.pu_syntax_states.reshape(-1))
-        if cu_close:        # coding_unit()'s contexts (HAVOC_CU_SYNTAX_CTX_*), per CTU, seeded the same way
-            crng = np.random.default_rng(seed + 7937)
-            self.cu_syntax_states = np.clip(crng.integers(4, 100, hmod.CU_SYNTAX_CTX_BYTES)[None, :] +
-                                            crng.integers(-6, 7, (self.cx * self.cy, hmod.CU_SYNTAX_CTX_BYTES)), 0, 125).astype(np.uint8)
-            self.d_cu_syntax_states = hv.up(self.cu_syntax_states.reshape(-1))
+            at = (y0 + self.PAD) * self.stride + x0 + self.PAD
+            fj = np.stack([np.arange(len(x0)) * nn * nn, at, y0 * width + x0, at], 1).astype(np.int32)
+            self.groups.append(dict(self._chain_group(log2, fj, (y0 // 64) * self.cx + x0 // 64), x0=x0, y0=y0, pj=np.zeros((len(x0), 8), np.int32),
+                                    d_pj=hv.zeros(len(x0) * 8, np.int32)))
+        self._cache = {}        # what the getters downloaded of the last step
+        self.rdoq_states, self.d_states = self._ctu_snapshots(seed + 7919, 128)
+        if tree_rates:      # the contexts outside the 128-byte snapshot (HAVOC_INTRA_SYNTAX_CTX_*: split_transform_flag's)
+            self.syntax_states, self.d_syntax_states = self._ctu_snapshots(seed + 7927, 4)
+        if pu_modes:        # prediction_unit()'s contexts (HAVOC_PU_SYNTAX_CTX_*)
+            self.pu_syntax_states, self.d_pu_syntax_states = self._ctu_snapshots(seed + 7933, hmod.PU_SYNTAX_CTX_BYTES)
+        if cu_close:        # coding_unit()'s contexts (HAVOC_CU_SYNTAX_CTX_*)
+            self.cu_syntax_states, self.d_cu_syntax_states = self._ctu_snapshots(seed + 7937, hmod.CU_SYNTAX_CTX_BYTES)
         self.pred = hv.zeros(width * height, self.dt)
         self.recon = hv.zeros(self.pe, self.dt)
         # chroma (round 4): Cb / Cr of source, list 0, list 1 in ONE allocation (plane k at k * cpe: 0-2 Cb, 3-5 Cr), their prediction and reconstruction planes
@@ -646,26 +673,20 @@ class DecisionPicture:
         if commit:          # the decided picture in buffers of its own, laid out as recon / crecon are; the cells: havoc.CQT_CELL_DT per MinCb cell
             self.cqt_recon, self.cqt_crecon = hv.zeros(self.pe, self.dt), hv.zeros(2 * self.cpe, self.dt)
             self.cqt_cells = hv.zeros((height >> self.CQT_MIN_CB_LOG2) * (width >> self.CQT_MIN_CB_LOG2) * hmod.CQT_CELL_DT.itemsize, np.uint8)
-        if finish:          # the decided picture's block structure (havoc.CELL_DT per 4x4 cell) and the loop filter's edge data on the region grid (as d_data / d_bs)
-            regions = ((width + 63) // 64 * 8 + 1) * ((height + 63) // 64 * 8 + 1)
-            self.cqt_block = hv.zeros((height // 4) * (width // 4) * hmod.CELL_DT.itemsize, np.uint8)
-            self.cqt_data, self.cqt_bs = hv.zeros(regions, np.uint8), hv.zeros(regions, np.uint8)     # (data: int8 values)
         if self.motion is not None:     # the decided picture's collocated motion store: havoc.COL_CELL_DT per 16x16 luma samples, dense rows
             if len(self.motion) != 3:
                 raise ValueError("motion must be (poc, ref_poc0, ref_poc1)")
             self.cqt_store = hv.zeros(((height + 15) // 16) * ((width + 15) // 16) * hmod.COL_CELL_DT.itemsize, np.uint8)
-        if self.col is not None:        # the units' table on the device (as the search's own copy of it is laid out) and a record per (unit, list)
+        if self.col is not None:        # a record per (unit, list)
             missing = {"store", "col_poc", "cur_poc", "target_poc", "all_backwards", "collocated_from_l0"} ^ set(self.col)
             if missing:
                 raise ValueError("col= takes exactly store, col_poc, cur_poc, target_poc, all_backwards, collocated_from_l0: %s" % sorted(missing))
             c = self.col
             self._temporal_params = hmod.temporal_params(width, height, self.CQT_CTB_LOG2, c["col_poc"], c["cur_poc"], c["target_poc"], c["all_backwards"],
                                                          c["collocated_from_l0"])
-            self._d_temporal_pus = hv.up(np.ascontiguousarray(self.pus).view(np.uint8).reshape(-1))
             self._d_temporal = hv.zeros(max(1, 2 * len(self.pus)) * hmod.TEMPORAL_CAND_DT.itemsize, np.uint8)
-        if self.merge_lists is not None:    # a record per searched unit; the units' table as the temporal candidates read it (shared with col= where both are given)
+        if self.merge_lists is not None:    # a record per searched unit
             self._merge_params = hmod.merge_params(width, height, self.CQT_CTB_LOG2, self.CQT_MIN_CB_LOG2, self.merge_lists, self.motion[1:3])
-            self._d_merge_pus = self._d_temporal_pus if self.col is not None else hv.up(np.ascontiguousarray(self.pus).view(np.uint8).reshape(-1))
             self.cqt_merge = hv.zeros(max(1, len(self.pus)) * hmod.MERGE_LIST_DT.itemsize, np.uint8)
         # ---- the intra candidates of the picture (an inter picture evaluates them per coding unit): partitions with neighbours from the source
         self.intra_parts = {}
@@ -676,7 +697,76 @@ class DecisionPicture:
                 self.intra_parts[log2] = dict(jobs=jobs, nb=nb, ictx=ictx, ctu=ctu, d_jobs=hv.up(jobs), d_nb=hv.up(nb),
                                               d_ictx=hv.up(np.ascontiguousarray(ictx).view(np.int32)), d_ctu=hv.up(np.ascontiguousarray(ctu, np.int32)),
                                               d_rec=hv.zeros(len(jobs) << (2 * log2), self.dt))
+        self._filter_buffers()
+        self._constructed = tuple(self.__dict__)      # (what a band view shares with its picture: _band_views)
         hv.sync()
+
+    def _ctu_snapshots(self, seed, nbytes):
+        """one snapshot of nbytes CABAC context states per CTU, seeded: a base state per context (drawn first), a jitter per CTU, limited to the valid states.
+        Returns (uint8 [CTUs, nbytes], its device copy)"""
+        rng = np.random.default_rng(seed)
+        base = rng.integers(4, 100, nbytes)
+        states = np.clip(base[None, :] + rng.integers(-6, 7, (self.cx * self.cy, nbytes)), 0, 125).astype(np.uint8)
+        return states, self.hv.up(states.reshape(-1))
+
+    def _up_records(self, records):
+        """a table of records of any layout as a uint8 device tensor"""
+        return self.hv.up(np.ascontiguousarray(records).view(np.uint8).reshape(-1))
+
+    def _zeros64(self, n):
+        with self.torch.cuda.stream(self.hv.tstream):
+            return self.torch.zeros(n, dtype=self.torch.int64, device=self.hv.device)
+
+    def _pus_table(self):
+        """self.pus on the device, laid out as the search's own copy of it is; it goes up once, for every launch that reads it"""
+        if not hasattr(self, "_d_pus"):
+            self._d_pus = self._up_records(self.pus)
+        return self._d_pus
+
+    # ---- the transform chain: residual + forward transform -> Rdoq::runQuantisation -> de-quantise + inverse transform + add -> SSD, over GROUPS of blocks of one size.
+    # A group's job table (int32 [m, 4]) names per block its slot in the group's buffers and its source, prediction and reconstruction blocks by sample offsets
+    # (tu_plan.py has the formats) ---------------------------------------------------------------------------------------------------------------------------------
+    def _chain_group(self, log2, jobs, ctx_index, c_idx=0, pieces=False, final=False, stats=False, rates=False):
+        """the RDOQ records and the buffers of the group of 2^log2 blocks that `jobs` names.  pieces: a buffer of reconstructed blocks, slot by slot (for candidates,
+        which are compared before one of them goes into the picture); final: the job records the decision writes for the last reconstruction, and its SSDs; stats:
+        the level statistics of the stand-in rate; rates: a CABAC rate per block"""
+        hv, m, area = self.hv, len(jobs), 1 << 2 * log2
+        rj, inv, dshift = tu_plan.rdoq_jobs(self.qp, self.bd, self.lam, log2, jobs[:, 0], ctx_index, c_idx)
+        g = dict(log2=log2, nn=1 << log2, m=m, inv=inv, dshift=dshift, jobs=jobs, d_jobs=hv.up(jobs), d_rj=self._up_records(rj), coef=hv.zeros(m * area, np.int16),
+                 level=hv.zeros(m * area, np.int16), cbf=hv.zeros(m, np.int32), ssd=hv.zeros(m, np.uint32), work=hv.rdoq_workspace(m))
+        if pieces:
+            g["piece"] = hv.zeros(m * area, self.dt)
+        if final:
+            g["d_fin"], g["ssd2"] = hv.zeros(m * 4, np.int32).view(-1, 4), hv.zeros(m, np.uint32)
+        if stats:
+            g["d_sj"], g["stats"] = hv.up(np.stack([jobs[:, 0], np.full(m, area)], 1).astype(np.int32)), hv.zeros(2 * m, np.int32)
+        if rates:
+            g["rates"] = self._zeros64(m)
+        return g
+
+    def _chain(self, groups, src, src_stride, pred, pred_stride, dst=None, dst_stride=None, then=None):
+        """the chain of every group: blocks of the planes src and pred, reconstructed into the plane dst -- or, without one, into the group's pieces; then(g)
+        (optional) issues what follows a group's three launches.  Asynchronous"""
+        hv, bd = self.hv, self.bd
+        for g in groups:
+            rec, rec_stride = (g["piece"], g["nn"]) if dst is None else (dst, dst_stride)
+            hv.tu_forward_d(bd, 0, g["log2"], g["coef"], src, src_stride, pred, pred_stride, g["d_jobs"])
+            hv.rdoq_d(bd, g["log2"], g["level"], g["coef"], self.d_states, g["d_rj"], g["cbf"], g["work"])
+            hv.tu_reconstruct_d(bd, 0, g["log2"], g["inv"], g["dshift"], rec, rec_stride, pred, pred_stride, src, src_stride, g["level"], g["d_jobs"], g["ssd"])
+            if then is not None:
+                then(g)
+
+    def _chain_final(self, groups, src, src_stride, pred, pred_stride, dst, dst_stride):
+        """every candidate reconstructed once more from its levels by the records the decision wrote (final=True): the chosen ones into the plane dst, the others
+        into the dump block"""
+        for g in groups:
+            self.hv.tu_reconstruct_d(self.bd, 0, g["log2"], g["inv"], g["dshift"], dst, dst_stride, pred, pred_stride, src, src_stride, g["level"], g["d_fin"], g["ssd2"])
+
+    def _tree_rates(self, plan):
+        """the whole-tree rate and cbf mask per (unit size, depth) of a tree plan, from the levels its chains left"""
+        for (L, depth), t in plan["tree_jobs"].items():
+            self.hv.tree_rate_d(L, depth, plan["sizes"][t["luma"]]["level"], plan["csizes"][t["chroma"]]["level"], self.d_states, self.d_syntax_states, t["d_jobs"],
+                                plan["tree_rate"], plan["tree_cbf"])
 
     def phase_planes(self):
         hv, pe, S = self.hv, self.pe, self.S
@@ -778,13 +868,12 @@ class DecisionPicture:
                 hv.satd_d(ref, p["stride"], p["d_dst"], p["size"], p["d_sj"], self.d_merge_satd[p["at"]:p["at"] + g["m"]], p["size"], p["size"])
             sat = [self.d_merge_satd[p["at"]:p["at"] + g["m"]] for p in q]
             hv.merge_decide_d(sat[0], sat[1], sat[2], len(g["sel"]), lam_q16, g["d_cost"], g["d_best"])
-        self._merge = None
 
     @property
     def merge(self):
         """what merge_candidates() left on the device, as numpy: dict(vectors int16 [units, 5, 2 lists, 2], satd [units, 5, 3 planes], cost [units, 5] (Q16),
         best [units])"""
-        if getattr(self, "_merge", None) is None:
+        if "merge" not in self._cache:
             hv, u, K = self.hv, self.units, self.MERGE_CANDIDATES
             flat = hv.down(self.d_merge_satd, np.int32)
             vec, satd = np.zeros((len(u), K, 2, 2), np.int16), np.zeros((len(u), K, 3), np.int64)
@@ -796,8 +885,8 @@ class DecisionPicture:
                 with self.torch.cuda.stream(hv.tstream):
                     cost[g["sel"]] = g["d_cost"].cpu().numpy().reshape(-1, K)
                 best[g["sel"]] = hv.down(g["d_best"], np.int32)
-            self._merge = dict(vectors=vec, satd=satd, cost=cost, best=best)
-        return self._merge
+            self._cache["merge"] = dict(vectors=vec, satd=satd, cost=cost, best=best)
+        return self._cache["merge"]
 
     # ---- the inter mode of every searched prediction unit (go2, turing/Search.hpp:1844-1902) ---------------------------------------------------------
     PU_CANDIDATES = 3       # L0, L1, bi: the order go2 tries them in for a 2Nx2N unit
@@ -913,7 +1002,6 @@ class DecisionPicture:
                     P["d_cand_mv"] = hv.zeros(cand_mv.size, np.int16)
                 P["cand_mv"] = cand_mv
                 P["d_cand_mv"].copy_(torch.from_numpy(cand_mv.reshape(-1)))
-        self._pu_decisions = None
 
     def pu_mode_launches(self):
         """measurePuCost and go2's comparison as batches over the tables pu_candidates() uploaded: per unit size and plane HavocPredUni of the L0 and L1 candidates,
@@ -936,15 +1024,15 @@ class DecisionPicture:
     def pu_decisions(self):
         """what pu_mode_launches() left on the device, as numpy, per unit of self.pus: dict(mode [n] (0 L0, 1 L1, 2 bi), cost [n] (Q16), costs [n, 3], syntax [n, 16]
         (the winner's snapshot), rates [n, 3] (Q16), satd [n, 3 candidates, 3 planes], jobs [n, 3] (PU_RATE_JOB_DT as uploaded))"""
-        if getattr(self, "_pu_decisions", None) is None:
+        if "pu_modes" not in self._cache:
             hv, P, K = self.hv, self._pu_plan(), self.PU_CANDIDATES
             M, at = P["M"], P["first"][:, None] + np.arange(K)[None, :]
             satd = hv.down(P["d_satd"], np.int32).reshape(3, M)
-            self._pu_decisions = dict(mode=hv.down(P["d_best"], np.int32), cost=hv.down(P["d_best_cost"], np.int64), costs=hv.down(P["d_cost"], np.int64)[at],
+            self._cache["pu_modes"] = dict(mode=hv.down(P["d_best"], np.int32), cost=hv.down(P["d_best_cost"], np.int64), costs=hv.down(P["d_cost"], np.int64)[at],
                                       syntax=hv.down(P["d_best_syntax"], np.uint8).reshape(-1, self.hmod.PU_SYNTAX_CTX_BYTES),
                                       rates=hv.down(P["d_rate"], np.int64)[at], satd=np.stack([satd[c][at] for c in range(3)], 2),
                                       jobs=hv.down(P["d_jobs"], np.uint8).view(self.hmod.PU_RATE_JOB_DT)[at])
-        return self._pu_decisions
+        return self._cache["pu_modes"]
 
     # ---- closing every transform-tree unit as an inter coding unit (Search<IfCbf<rqt_root_cbf, transform_tree>>::go, turing/Search.hpp:2362-2568) -------------
     def _cu_plan(self):
@@ -1008,13 +1096,13 @@ class DecisionPicture:
         rate charged is the WINNER's of pu_decide, from the winner's snapshot."""
         if not self.cu_close:
             raise ValueError("cu_decisions: the picture was made without cu_close=True")
-        if getattr(self, "_cu_decisions", None) is None:
+        if "cu_close" not in self._cache:
             hv, Q, hmod = self.hv, self._cu_plan(), self.hmod
-            self._cu_decisions = dict(records=hv.down(Q["d_out"], np.uint8).view(hmod.CU_CHOICE_DT).copy(),
+            self._cache["cu_close"] = dict(records=hv.down(Q["d_out"], np.uint8).view(hmod.CU_CHOICE_DT).copy(),
                                       cu_syntax=hv.down(Q["d_cu_after"], np.uint8).reshape(-1, hmod.CU_SYNTAX_CTX_BYTES),
                                       pu_syntax=hv.down(Q["d_pu_after"], np.uint8).reshape(-1, hmod.PU_SYNTAX_CTX_BYTES),
                                       pred_ssd=hv.down(Q["d_pred_ssd"], np.int32).reshape(-1, 3), jobs=Q["jobs"], searched=Q["match"])
-        return self._cu_decisions
+        return self._cache["cu_close"]
 
     # ---- the coding quadtree of every CTU over the closed units (Search<coding_quadtree>::go, turing/Search.hpp:808-886) ---------------------------------------
     CQT_CTB_LOG2, CQT_MIN_CB_LOG2 = 6, 3
@@ -1062,12 +1150,12 @@ class DecisionPicture:
         candidate, a node whose four sub-units were searched is compared, and every CTU is decided."""
         if not self.cqt:
             raise ValueError("cqt_decisions: the picture was made without cqt=True")
-        if getattr(self, "_cqt_decisions", None) is None:
+        if "cqt" not in self._cache:
             B = self._cqt_plan()
             work = self.hv.down(B["work"], np.int64)        # [CTUs]: the published words; then the row ticket (low half) and the give-up word (high half)
-            self._cqt_decisions = dict(node_cu=B["node_cu"], gave_up=bool(work[self.cx * self.cy] >> 32),
+            self._cache["cqt"] = dict(node_cu=B["node_cu"], gave_up=bool(work[self.cx * self.cy] >> 32),
                                        **self.hv.cqt_download(B, self.W, self.H, self.CQT_CTB_LOG2, self.CQT_MIN_CB_LOG2))
-        return self._cqt_decisions
+        return self._cache["cqt"]
 
     # ---- acting on the decision: the final units of every decided CTU into one picture and a per-cell field (havoc_mi355x_cqt_commit) ----------------------------
     def cqt_commit_launch(self):
@@ -1090,13 +1178,13 @@ class DecisionPicture:
             raise ValueError("cqt_commit_results: the picture was made without commit=True")
         if self.finish:
             raise ValueError("cqt_commit_results: with finish=True the committed planes are filtered in place: cqt_finish_results() has them")
-        if getattr(self, "_cqt_commit", None) is None:
+        if "commit" not in self._cache:
             hv, pad, c2 = self.hv, self.PAD, self.PAD // 2
             y = hv.down(self.cqt_recon, self.dt)[:self.n].reshape(-1, self.stride)[pad:pad + self.H, pad:pad + self.W]
             c = hv.down(self.cqt_crecon, self.dt)
             c = np.stack([c[k * self.cpe:k * self.cpe + self.cn].reshape(-1, self.cstride)[c2:c2 + self.H // 2, c2:c2 + self.W // 2] for k in range(2)])
-            self._cqt_commit = dict(recon=y.copy(), crecon=c, cells=hv.cqt_cells_download(self.cqt_cells, self.W, self.H, self.CQT_MIN_CB_LOG2))
-        return self._cqt_commit
+            self._cache["commit"] = dict(recon=y.copy(), crecon=c, cells=hv.cqt_cells_download(self.cqt_cells, self.W, self.H, self.CQT_MIN_CB_LOG2))
+        return self._cache["commit"]
 
     # ---- the committed picture's motion as the next picture's collocated store (turing/StateCollocatedMotion.h:51-122) -------------------------------------------
     def cqt_motion_launch(self):
@@ -1109,30 +1197,30 @@ class DecisionPicture:
         """what cqt_motion_launch() left on the device, as numpy: havoc.COL_CELL_DT [(H + 15) // 16, (W + 15) // 16]"""
         if self.motion is None:
             raise ValueError("cqt_motion_results: the picture was made without motion=(poc, ref_poc0, ref_poc1)")
-        if getattr(self, "_cqt_motion", None) is None:
-            self._cqt_motion = self.hv.down(self.cqt_store, np.uint8).view(self.hmod.COL_CELL_DT).reshape((self.H + 15) // 16, (self.W + 15) // 16).copy()
-        return self._cqt_motion
+        if "motion" not in self._cache:
+            self._cache["motion"] = self.hv.down(self.cqt_store, np.uint8).view(self.hmod.COL_CELL_DT).reshape((self.H + 15) // 16, (self.W + 15) // 16).copy()
+        return self._cache["motion"]
 
     # ---- this picture's temporal candidates from another picture's store (turing/Mvp.h:44-181) --------------------------------------------------------------------
     def temporal_launch(self):
         """the temporal candidate of every unit of self.pus, per list, from col["store"] (dense rows).  It reads nothing this picture's step writes.  One launch;
         asynchronous.  Ordering against the step that writes the store is the caller's (see __init__)"""
-        self.hv.temporal_candidates_d(self._temporal_params, self.col["store"], (self.W + 15) // 16, self._d_temporal_pus, len(self.pus), self._d_temporal)
+        self.hv.temporal_candidates_d(self._temporal_params, self.col["store"], (self.W + 15) // 16, self._pus_table(), len(self.pus), self._d_temporal)
 
     def temporal_candidates(self):
         """what temporal_launch() left on the device, as numpy: havoc.TEMPORAL_CAND_DT [len(self.pus), 2] (unit, list)"""
         if self.col is None:
             raise ValueError("temporal_candidates: the picture was made without col=")
-        if getattr(self, "_temporal", None) is None:
+        if "col" not in self._cache:
             n = len(self.pus)
-            self._temporal = self.hv.down(self._d_temporal, np.uint8)[:2 * n * self.hmod.TEMPORAL_CAND_DT.itemsize].view(self.hmod.TEMPORAL_CAND_DT).reshape(n, 2).copy()
-        return self._temporal
+            self._cache["col"] = self.hv.down(self._d_temporal, np.uint8)[:2 * n * self.hmod.TEMPORAL_CAND_DT.itemsize].view(self.hmod.TEMPORAL_CAND_DT).reshape(n, 2).copy()
+        return self._cache["col"]
 
     # ---- the committed picture's merge candidate lists (turing/Mvp.h:486-716) -----------------------------------------------------------------------------------
     def cqt_merge_launch(self):
         """behind cqt_commit_launch and, with col=, behind temporal_launch: the merge candidate list of every final coding unit from cqt_cells (the neighbours in their
         final state) and this picture's temporal records, into cqt_merge.  One launch; asynchronous"""
-        self.hv.cqt_merge_lists_d(self._merge_params, self.cqt_cells, self._d_merge_pus, len(self.pus), self._d_temporal if self.col is not None else None,
+        self.hv.cqt_merge_lists_d(self._merge_params, self.cqt_cells, self._pus_table(), len(self.pus), self._d_temporal if self.col is not None else None,
                                   self.cqt_merge)
 
     def cqt_merge_results(self):
@@ -1140,9 +1228,9 @@ class DecisionPicture:
         bytes with match -1"""
         if self.merge_lists is None:
             raise ValueError("cqt_merge_results: the picture was made without merge_lists=max_cand")
-        if getattr(self, "_cqt_merge", None) is None:
-            self._cqt_merge = self.hv.cqt_merge_lists_download(self.cqt_merge, len(self.pus))
-        return self._cqt_merge
+        if "merge_lists" not in self._cache:
+            self._cache["merge_lists"] = self.hv.cqt_merge_lists_download(self.cqt_merge, len(self.pus))
+        return self._cache["merge_lists"]
 
     # ---- the committed picture finished: block structure, boundary strengths, deblocking, padding (turing/TaskDeblock.cpp:105-167) --------------------------------
     def cqt_finish_launch(self):
@@ -1162,26 +1250,21 @@ class DecisionPicture:
         whole padded chroma planes; cells havoc.CELL_DT [H / 4, W / 4]; data int8, bs uint8: the region grid's edge data)"""
         if not self.finish:
             raise ValueError("cqt_finish_results: the picture was made without finish=True")
-        if getattr(self, "_cqt_finish", None) is None:
+        if "finish" not in self._cache:
             hv = self.hv
             c = hv.down(self.cqt_crecon, self.dt)
-            self._cqt_finish = dict(recon=hv.down(self.cqt_recon, self.dt)[:self.n].reshape(-1, self.stride).copy(),
+            self._cache["finish"] = dict(recon=hv.down(self.cqt_recon, self.dt)[:self.n].reshape(-1, self.stride).copy(),
                                     crecon=np.stack([c[k * self.cpe:k * self.cpe + self.cn].reshape(-1, self.cstride) for k in range(2)]),
                                     cells=hv.down(self.cqt_block, np.uint8).view(self.hmod.CELL_DT).reshape(self.H // 4, self.W // 4).copy(),
                                     data=hv.down(self.cqt_data, np.int8).copy(), bs=hv.down(self.cqt_bs, np.uint8).copy())
-        return self._cqt_finish
+        return self._cache["finish"]
 
     def chroma_chain(self, field):
         """the inter residual of the chroma planes at the decided vectors (turing/Reconstruct.cpp:1274-1286 with cIdx 1, 2): HavocPredUni 4-tap of every unit's
-        Cb and Cr block at its list-0 vector (eighth-sample phase = the luma vector's low three bits), then residual + DCT -> Rdoq::runQuantisation (cIdx) ->
-        de-quantise + inverse DCT + add -> SSD, one chain per chroma transform size, into the chroma reconstruction planes.  Asynchronous."""
-        hv, bd = self.hv, self.bd
-        hw = self.W // 2
+        Cb and Cr block at its list-0 vector (eighth-sample phase = the luma vector's low three bits), then the chain (Rdoq::runQuantisation with cIdx), one per
+        chroma transform size and component, into the chroma reconstruction planes.  Asynchronous."""
         self.chroma_predict()
-        for g in self.cgroups:
-            hv.tu_forward_d(bd, 0, g["log2"], g["coef"], self.d_cpic, self.cstride, self.cpred, hw, g["d_fj"])
-            hv.rdoq_d(bd, g["log2"], g["level"], g["coef"], self.d_states, g["d_rj"], g["cbf"], g["work"])
-            hv.tu_reconstruct_d(bd, 0, g["log2"], g["inv"], g["dshift"], self.crecon, self.cstride, self.cpred, hw, self.d_cpic, self.cstride, g["level"], g["d_fj"], g["ssd"])
+        self._chain(self.cgroups, self.d_cpic, self.cstride, self.cpred, self.W // 2, self.crecon, self.cstride)
 
     def chroma_predict(self):
         """the prediction half of chroma_chain alone: every unit's Cb and Cr block at its decided vector into cpred (tree_rates=True: the chroma candidates of both
@@ -1190,205 +1273,115 @@ class DecisionPicture:
         self._chroma_groups()
         for g in self.cgroups:
             hv.pred_jobs_d(self.layout, self.d_field, 0, g["d_x0"], g["d_y0"], g["log2"] + 1, g["comp"], g["d_dst"], g["d_pj"])
-            hv.pred_uni_d(4, self.bd, self.cpred, self.W // 2, self.d_cpic, self.cstride, g["d_pj"].view(-1, 8), g["cn"], g["cn"])
+            hv.pred_uni_d(4, self.bd, self.cpred, self.W // 2, self.d_cpic, self.cstride, g["d_pj"].view(-1, 8), g["nn"], g["nn"])
 
     def _chroma_groups(self):
         """chroma_chain's job tables and buffers per (unit size, component), built once"""
-        hv, bd, torch, hmod = self.hv, self.bd, self.torch, self.hmod
-        from . import workload
-        u = self.units
-        hw, hh = self.W // 2, self.H // 2
-        if not hasattr(self, "cgroups"):
-            self.cgroups = []
-            for log2 in (5, 4, 3):
-                sel = np.flatnonzero(u["log2_size"] == log2)
-                if not len(sel):
-                    continue
-                cl, cn, m = log2 - 1, 1 << (log2 - 1), len(sel)
-                x0, y0 = u["x0"][sel].astype(np.int64) // 2, u["y0"][sel].astype(np.int64) // 2
-                qs, qshift, _ = workload.quant_params(self.qp, cl, bd, False)
-                inv, dshift = workload.dequant_params(self.qp, cl, bd)
-                lq, sf = hmod.rdoq_lambda(self.lam, inv)
-                for comp in (1, 2):
-                    fj = np.zeros((m, 4), np.int32)
-                    fj[:, 0] = np.arange(m) * cn * cn
-                    fj[:, 1] = 3 * (comp - 1) * self.cpe + (y0 + self.PAD // 2) * self.cstride + x0 + self.PAD // 2          # source block in d_cpic
-                    fj[:, 2] = (comp - 1) * hw * hh + y0 * hw + x0                                                           # prediction block in cpred
-                    fj[:, 3] = (comp - 1) * self.cpe + (y0 + self.PAD // 2) * self.cstride + x0 + self.PAD // 2              # reconstruction in crecon
-                    jobs = np.zeros(m, hmod.RDOQ_JOB_DT)
-                    jobs["dst_off"] = jobs["src_off"] = fj[:, 0]
-                    jobs["quant_scale"], jobs["quant_shift"], jobs["inv_scale"], jobs["lambda_q16"], jobs["sdh_factor"] = qs, qshift, inv, lq, sf
-                    jobs["sdh"], jobs["c_idx"] = 1, comp
-                    jobs["ctx_index"] = (u["y0"][sel] // 64) * self.cx + u["x0"][sel] // 64
-                    with torch.cuda.stream(hv.tstream):
-                        d_rj = torch.from_numpy(jobs.view(np.uint8).reshape(-1)).to(hv.device)
-                    self.cgroups.append(dict(log2=cl, cn=cn, comp=comp, m=m, sel=sel, inv=inv, dshift=dshift, d_fj=hv.up(fj), d_rj=d_rj,
-                                             d_x0=hv.up(u["x0"][sel].astype(np.int32)), d_y0=hv.up(u["y0"][sel].astype(np.int32)), d_dst=hv.up(fj[:, 2]),
-                                             d_pj=hv.zeros(m * 8, np.int32), coef=hv.zeros(m * cn * cn, np.int16),
-                                             level=hv.zeros(m * cn * cn, np.int16), cbf=hv.zeros(m, np.int32), ssd=hv.zeros(m, np.uint32), work=hv.rdoq_workspace(m)))
+        if hasattr(self, "cgroups"):
+            return
+        hv, u = self.hv, self.units
+        hw, hh, c2 = self.W // 2, self.H // 2, self.PAD // 2
+        self.cgroups = []
+        for log2 in (5, 4, 3):
+            sel = np.flatnonzero(u["log2_size"] == log2)
+            if not len(sel):
+                continue
+            cl, m = log2 - 1, len(sel)
+            x0, y0 = u["x0"][sel].astype(np.int64) // 2, u["y0"][sel].astype(np.int64) // 2
+            at = (y0 + c2) * self.cstride + x0 + c2
+            for comp in (1, 2):
+                # the block's slot; its source in d_cpic, its prediction in cpred, its reconstruction in crecon
+                fj = np.stack([np.arange(m) << 2 * cl, 3 * (comp - 1) * self.cpe + at, (comp - 1) * hw * hh + y0 * hw + x0, (comp - 1) * self.cpe + at], 1).astype(np.int32)
+                # (cn: the block size under the name the readers of this list know it by; every group has it as nn)
+                self.cgroups.append(dict(self._chain_group(cl, fj, u["ctx_index"][sel], comp), cn=1 << cl, comp=comp, sel=sel, d_x0=hv.up(u["x0"][sel].astype(np.int32)),
+                                         d_y0=hv.up(u["y0"][sel].astype(np.int32)), d_dst=hv.up(fj[:, 2]), d_pj=hv.zeros(m * 8, np.int32)))
 
     def tu_chain(self, field, predicted=False):
         """prediction at the decided vectors, then the residual-quadtree decisions and the reconstruction; returns (decisions, stats)"""
         if not predicted:
             self.predict(field)
         base = self.d_pic.data_ptr()
-        self._rqt, st = rqt(self.hv.h, self.S, self.bd, base, self.origin, self.stride, self.pred.data_ptr(), self.W, self.recon.data_ptr(), self.origin,
+        self.rqt_results, st = rqt(self.hv.h, self.S, self.bd, base, self.origin, self.stride, self.pred.data_ptr(), self.W, self.recon.data_ptr(), self.origin,
                                    self.stride, self.d_states.data_ptr(), self.quant, self.lam, 1.0 / self.lam, self.units)
         self.rqt_stats = st
-        return self._rqt, st
+        return self.rqt_results, st
 
     # ---- round 4: the transform-tree decision and the block structure on the device -- nothing of the picture's step waits for the host after its searches ----
-    def _rqt_plan(self):
-        """what havoc_search_rqt builds per call, built ONCE (the units of a picture do not move): per transform size the candidates' job records (depth 0 of every unit
-        of that size, then the four depth-1 blocks of every unit of the next larger size, unit by unit), their buffers, and where each unit finds its candidates"""
-        hv, hmod, torch = self.hv, self.hmod, self.torch
-        from . import workload
-        u = self.units
-        lists = {s: [] for s in (2, 3, 4, 5)}
-        zero_at, one_at = np.zeros(len(u), np.int32), np.zeros(len(u), np.int32)
-        for i in range(len(u)):
-            L = int(u["log2_size"][i])
-            zero_at[i] = len(lists[L])
-            lists[L].append((i, 0, 0))
-            one_at[i] = len(lists[L - 1])
-            lists[L - 1] += [(i, 1, k) for k in range(4)]
-        plan = dict(sizes={}, d_units=hv.up(np.ascontiguousarray(u).view(np.int32)), d_zero_at=hv.up(zero_at), d_one_at=hv.up(one_at),
-                    d_out=hv.zeros(len(u) * 26, np.int32), table=np.zeros((4, 5), np.uint64), rates=np.zeros(4, np.uint64), launches=0)
-        for log2, cand in lists.items():
-            m = len(cand)
-            if not m:
-                continue
-            nn = 1 << log2
-            area = nn * nn
-            c = np.array(cand, np.int64)
-            x = u["x0"][c[:, 0]].astype(np.int64) + np.where(c[:, 1] == 1, (c[:, 2] & 1) * nn, 0)
-            y = u["y0"][c[:, 0]].astype(np.int64) + np.where(c[:, 1] == 1, (c[:, 2] >> 1) * nn, 0)
-            jobs = np.stack([np.arange(m) * area, self.origin + y * self.stride + x, y * self.W + x, np.arange(m) * area], 1).astype(np.int32)
-            qs, qshift, inv, dshift = (int(v) for v in self.quant[log2 - 2])
-            rj = np.zeros(m, hmod.RDOQ_JOB_DT)
-            rj["dst_off"] = rj["src_off"] = jobs[:, 0]
-            rj["quant_scale"], rj["quant_shift"], rj["inv_scale"] = qs, qshift, inv
-            rj["lambda_q16"], rj["sdh_factor"] = hmod.rdoq_lambda(self.lam, inv)
-            rj["sdh"] = 1
-            rj["ctx_index"] = u["ctx_index"][c[:, 0]]
-            with torch.cuda.stream(hv.tstream):
-                d_rj = torch.from_numpy(rj.view(np.uint8).reshape(-1)).to(hv.device)
-            g = dict(log2=log2, nn=nn, m=m, inv=inv, dshift=dshift, d_jobs=hv.up(jobs), d_fin=hv.zeros(m * 4, np.int32), d_rj=d_rj,
-                     d_sj=hv.up(np.stack([jobs[:, 0], np.full(m, area)], 1).astype(np.int32)), coef=hv.zeros(m * area, np.int16), level=hv.zeros(m * area, np.int16),
-                     piece=hv.zeros(m * area, self.dt), work=hv.rdoq_workspace(m), cbf=hv.zeros(m, np.int32), ssd=hv.zeros(m, np.uint32), stats=hv.zeros(2 * m, np.int32),
-                     ssd2=hv.zeros(m, np.uint32))
-            plan["sizes"][log2] = g
-            plan["table"][log2 - 2] = [g["cbf"].data_ptr(), g["ssd"].data_ptr(), g["stats"].data_ptr(), g["d_jobs"].data_ptr(), g["d_fin"].data_ptr()]
-            if self.residual_rates:
-                # a depth-0 candidate is a job of its own; the four depth-1 candidates of a unit lie one after the other: ONE job that walks them in z-order with the
-                # contexts running on, as the reference codes them -- each from the unit's snapshot, like the RDOQ jobs
-                lead = np.flatnonzero(c[:, 2] == 0)
-                qj = np.zeros(len(lead), hmod.RESIDUAL_RATE_JOB_DT)
-                qj["level_off"], qj["rate_index"], qj["ctx_index"] = jobs[lead, 0], lead, u["ctx_index"][c[lead, 0]]
-                qj["sdh"], qj["count"] = 1, np.where(c[lead, 1] == 1, 4, 1)
-                with torch.cuda.stream(hv.tstream):
-                    g["d_qj"] = torch.from_numpy(qj.view(np.uint8).reshape(-1).copy()).to(hv.device)
-                    g["rates"] = torch.zeros(m, dtype=torch.int64, device=hv.device)
-                g["rate_jobs"] = qj
-                plan["table"][log2 - 2, 2] = 0      # (no level statistics: nonzero / sum_abs of the results are 0)
-                plan["rates"][log2 - 2] = g["rates"].data_ptr()
-            plan["launches"] += 5
-        plan["launches"] += 1
-        # a block-sized area nobody reads, inside the reconstruction's bottom border (rewritten by the padding that ends the step): where the candidates that lost go
-        plan["dump"] = (self.H + self.PAD + 16) * self.stride + self.PAD
-        plan["rl_q16"] = int((1.0 / self.lam) * 65536 + 0.5)
-        if self.tree_rates:
-            self._tree_plan(plan, zero_at, one_at)
-        self._filter_buffers()
+    def _tree_tables(self, u, plane, chroma, final=False, stats=False, rates=False):
+        """the tables and buffers of the transform-tree decisions of the units u (RQT_CU_DT), built ONCE (the units of a picture do not move): per transform size the
+        luma candidates' group, with chroma per chroma transform size the Cb / Cr candidates' group and the tree-rate jobs per (unit size, depth) -- laid out by
+        tu_plan.candidate_layout -- where each unit finds its candidates, and the decision's tables and outputs.  plane[i]: which of the unit prediction planes holds
+        unit i's prediction (plane p of luma at p W H, of Cb / Cr at 2 p and 2 p + 1 chroma planes; 0: the picture's own pred / cpred)"""
+        hv, n = self.hv, len(u)
+        W, hw, c2 = self.W, self.W // 2, self.PAD // 2
+        ypl, cpl = W * self.H, hw * (self.H // 2)
+        lay = tu_plan.candidate_layout(u["log2_size"])
+        x0, y0, ctx = u["x0"].astype(np.int64), u["y0"].astype(np.int64), u["ctx_index"]
+        row = lambda g: [g[k].data_ptr() if k in g else 0 for k in ("cbf", "ssd", "stats", "d_jobs", "d_fin")]      # (havoc_rqt_size; absent: not made on this route)
+        plan = dict(units=u, zero_at=lay["zero_at"], one_at=lay["one_at"], sizes={}, table=np.zeros((4, 5), np.uint64), rl_q16=int((1.0 / self.lam) * 65536 + 0.5),
+                    d_units=hv.up(np.ascontiguousarray(u).view(np.int32)), d_zero_at=hv.up(lay["zero_at"]), d_one_at=hv.up(lay["one_at"]),
+                    d_out=hv.zeros(n * 26, np.int32))
+        for log2, c in lay["luma"].items():
+            x, y = tu_plan.candidate_xy(x0, y0, c, log2)
+            slot = np.arange(len(c)) << 2 * log2
+            jobs = np.stack([slot, self.origin + y * self.stride + x, plane[c[:, 0]] * ypl + y * W + x, slot], 1).astype(np.int32)
+            g = plan["sizes"][log2] = dict(self._chain_group(log2, jobs, ctx[c[:, 0]], pieces=True, final=final, stats=stats, rates=rates), cand=c)
+            plan["table"][log2 - 2] = row(g)
+        if not chroma:
+            return plan
+        plan.update(csizes={}, ctable=np.zeros((4, 5), np.uint64), chroma_at=lay["chroma_at"], d_chroma_at=hv.up(np.ascontiguousarray(lay["chroma_at"]).view(np.int32)),
+                    tree_rate=self._zeros64(2 * n), tree_cbf=hv.zeros(2 * n, np.int32), d_tree_out=hv.zeros(4 * n, np.int32))
+        for cl, c in lay["chroma"].items():
+            x, y = tu_plan.candidate_xy(x0, y0, c, cl, chroma=True)
+            comp, slot = c[:, 2], np.arange(len(c)) << 2 * cl
+            jobs = np.stack([slot, 3 * (comp - 1) * self.cpe + (y + c2) * self.cstride + x + c2, (2 * plane[c[:, 0]] + comp - 1) * cpl + y * hw + x, slot], 1).astype(np.int32)
+            g = plan["csizes"][cl] = dict(self._chain_group(cl, jobs, ctx[c[:, 0]], comp, pieces=True, final=final), cand=c)
+            plan["ctable"][cl - 2] = row(g)
+        plan["tree_jobs"] = {key: dict(jobs=tj, d_jobs=self._up_records(tj), luma=luma, chroma=chroma_size)
+                             for key, (tj, luma, chroma_size) in tu_plan.tree_rate_jobs(lay, u["log2_size"], ctx).items()}
         return plan
 
-    def _tree_plan(self, plan, zero_at, one_at):
-        """tree_rates=True, beside the luma candidates of _rqt_plan: the chroma candidates of both depths per chroma transform size (a unit's depth-0 Cb and Cr block
-        of max(L - 1, 2); for L > 3 its four depth-1 Cb blocks, then its four Cr blocks, of L - 2, z-order; an 8x8 unit's one 4x4 block per component serves both
-        depths), where each unit finds them, and the tree_rate jobs per (unit size, depth) -- every tree from the unit's snapshot, out_index = 2 * unit + depth"""
-        hv, hmod, torch, bd = self.hv, self.hmod, self.torch, self.bd
-        from . import workload
-        u = self.units
-        hw, hh, c2 = self.W // 2, self.H // 2, self.PAD // 2
-        clists = {s: [] for s in (2, 3, 4)}
-        chroma_at = np.zeros(len(u), hmod.RQT_CHROMA_AT_DT)
-        for i in range(len(u)):
-            L = int(u["log2_size"][i])
-            c0 = max(L - 1, 2)
-            chroma_at[i]["cb_zero"], chroma_at[i]["cr_zero"] = len(clists[c0]), len(clists[c0]) + 1
-            clists[c0] += [(i, 0, 1, 0), (i, 0, 2, 0)]
-            if L > 3:
-                chroma_at[i]["cb_one"], chroma_at[i]["cr_one"] = len(clists[L - 2]), len(clists[L - 2]) + 4
-                clists[L - 2] += [(i, 1, comp, k) for comp in (1, 2) for k in range(4)]
-            else:
-                chroma_at[i]["cb_one"], chroma_at[i]["cr_one"] = chroma_at[i]["cb_zero"], chroma_at[i]["cr_zero"]
-        plan["chroma_at"], plan["d_chroma_at"] = chroma_at, hv.up(np.ascontiguousarray(chroma_at).view(np.int32))
-        plan["csizes"], plan["ctable"] = {}, np.zeros((4, 5), np.uint64)
-        for cl, cand in clists.items():
-            m = len(cand)
-            if not m:
-                continue
-            cn = 1 << cl
-            area = cn * cn
-            c = np.array(cand, np.int64)
-            x = u["x0"][c[:, 0]].astype(np.int64) // 2 + np.where(c[:, 1] == 1, (c[:, 3] & 1) * cn, 0)
-            y = u["y0"][c[:, 0]].astype(np.int64) // 2 + np.where(c[:, 1] == 1, (c[:, 3] >> 1) * cn, 0)
-            comp = c[:, 2]
-            jobs = np.stack([np.arange(m) * area, 3 * (comp - 1) * self.cpe + (y + c2) * self.cstride + x + c2, (comp - 1) * hw * hh + y * hw + x,
-                             np.arange(m) * area], 1).astype(np.int32)
-            qs, qshift, _ = workload.quant_params(self.qp, cl, bd, False)
-            inv, dshift = workload.dequant_params(self.qp, cl, bd)
-            rj = np.zeros(m, hmod.RDOQ_JOB_DT)
-            rj["dst_off"] = rj["src_off"] = jobs[:, 0]
-            rj["quant_scale"], rj["quant_shift"], rj["inv_scale"] = qs, qshift, inv
-            rj["lambda_q16"], rj["sdh_factor"] = hmod.rdoq_lambda(self.lam, inv)
-            rj["sdh"], rj["c_idx"] = 1, comp
-            rj["ctx_index"] = u["ctx_index"][c[:, 0]]
-            with torch.cuda.stream(hv.tstream):
-                d_rj = torch.from_numpy(rj.view(np.uint8).reshape(-1)).to(hv.device)
-            g = dict(log2=cl, nn=cn, m=m, inv=inv, dshift=dshift, cand=c, d_jobs=hv.up(jobs), d_fin=hv.zeros(m * 4, np.int32), d_rj=d_rj, coef=hv.zeros(m * area, np.int16),
-                     level=hv.zeros(m * area, np.int16), piece=hv.zeros(m * area, self.dt), work=hv.rdoq_workspace(m), cbf=hv.zeros(m, np.int32), ssd=hv.zeros(m, np.uint32),
-                     ssd2=hv.zeros(m, np.uint32))
-            plan["csizes"][cl] = g
-            plan["ctable"][cl - 2] = [g["cbf"].data_ptr(), g["ssd"].data_ptr(), 0, g["d_jobs"].data_ptr(), g["d_fin"].data_ptr()]
-            plan["launches"] += 4
-        plan["table"][:, 2] = 0          # (no level statistics on this route: nonzero / sum_abs of the results are 0)
-        plan["tree_jobs"] = {}
-        for L in (5, 4, 3):
-            sel = np.flatnonzero(u["log2_size"] == L)
-            if not len(sel):
-                continue
-            c0, c1 = max(L - 1, 2), max(L - 2, 2)
-            for depth in (0, 1):
-                tj = np.zeros(len(sel), hmod.TREE_RATE_JOB_DT)
-                if depth == 0:
-                    tj["luma_off"], tj["cb_off"], tj["cr_off"] = zero_at[sel] << 2 * L, chroma_at["cb_zero"][sel] << 2 * c0, chroma_at["cr_zero"][sel] << 2 * c0
-                else:
-                    tj["luma_off"], tj["cb_off"], tj["cr_off"] = one_at[sel] << 2 * (L - 1), chroma_at["cb_one"][sel] << 2 * c1, chroma_at["cr_one"][sel] << 2 * c1
-                tj["ctx_index"], tj["out_index"], tj["sdh"] = u["ctx_index"][sel], 2 * sel + depth, 1
-                tj["flags"] = hmod.TREE_RATE_SPLIT_FLAG_CODED      # MaxTrafoDepth 1, MinTbLog2SizeY 2, MaxTbLog2SizeY 5: coded for every unit of 8 .. 32
-                with torch.cuda.stream(hv.tstream):
-                    d_tj = torch.from_numpy(tj.view(np.uint8).reshape(-1).copy()).to(hv.device)
-                plan["tree_jobs"][L, depth] = dict(jobs=tj, d_jobs=d_tj, luma=L - depth, chroma=c1 if depth else c0)
-                plan["launches"] += 1
-        with torch.cuda.stream(hv.tstream):
-            plan["tree_rate"] = torch.zeros(2 * len(u), dtype=torch.int64, device=hv.device)
-        plan["tree_cbf"], plan["d_tree_out"] = hv.zeros(2 * len(u), np.int32), hv.zeros(4 * len(u), np.int32)
-        # where the chroma candidates that lost go: inside the chroma reconstruction's bottom border (nothing reads it)
-        plan["cdump"] = (hh + c2 + 8) * self.cstride + c2
-        plan["launches"] += 4 * len(np.unique(u["log2_size"])) - len(plan["sizes"])      # (chroma prediction: 2 per unit size and component; no level_stats)
+    def _rqt_plan(self):
+        """the tree plan of self.units, the prediction in pred / cpred: what havoc_search_rqt builds per call.  The default route has the level statistics of the
+        stand-in rate; residual_rates=True a CABAC rate per luma candidate; tree_rates=True the chroma candidates and the whole trees' rates.  Every route
+        reconstructs the chosen candidates into the picture: final records"""
+        hmod, u = self.hmod, self.units
+        plan = self._tree_tables(u, np.zeros(len(u), np.int64), self.tree_rates, final=True, stats=not (self.residual_rates or self.tree_rates), rates=self.residual_rates)
+        plan["rates"] = np.zeros(4, np.uint64)
+        if self.residual_rates:
+            for log2, g in plan["sizes"].items():
+                # a depth-0 candidate is a job of its own; the four depth-1 candidates of a unit lie one after the other: ONE job that walks them in z-order with
+                # the contexts running on, as the reference codes them -- each from the unit's snapshot, like the RDOQ jobs
+                c = g["cand"]
+                lead = np.flatnonzero(c[:, 2] == 0)
+                qj = np.zeros(len(lead), hmod.RESIDUAL_RATE_JOB_DT)
+                qj["level_off"], qj["rate_index"], qj["ctx_index"] = g["jobs"][lead, 0], lead, u["ctx_index"][c[lead, 0]]
+                qj["sdh"], qj["count"] = 1, np.where(c[lead, 1] == 1, 4, 1)
+                g["rate_jobs"], g["d_qj"] = qj, self._up_records(qj)
+                plan["rates"][log2 - 2] = g["rates"].data_ptr()
+        plan["launches"] = 5 * len(plan["sizes"]) + 1
+        # a block-sized area nobody reads, inside the reconstruction's bottom border (rewritten by the padding that ends the step): where the candidates that lost go
+        plan["dump"] = (self.H + self.PAD + 16) * self.stride + self.PAD
+        if self.tree_rates:
+            # ... and the chroma candidates that lost: inside the chroma reconstruction's bottom border (nothing reads it)
+            plan["cdump"] = (self.H // 2 + self.PAD // 2 + 8) * self.cstride + self.PAD // 2
+            # (4 per chroma size, 1 per tree job, chroma prediction: 2 per unit size and component; no level_stats)
+            plan["launches"] += 4 * len(plan["csizes"]) + len(plan["tree_jobs"]) + 4 * len(np.unique(u["log2_size"])) - len(plan["sizes"])
+        return plan
 
     def _filter_buffers(self):
-        """the block structure and the loop filter's edge data of the picture (one set per picture, whatever decides its units -- the whole-picture plan or the band views)"""
-        if hasattr(self, "d_cells"):
-            return
+        """the block structure and the loop filter's edge data on the region grid: one set per picture, whatever decides its units -- the whole-picture plan, the band
+        views or the host route -- and with finish=True a second set for the committed picture (cqt_block: havoc.CELL_DT per 4x4 cell)"""
         hv, torch = self.hv, self.torch
-        n = ((self.W + 63) // 64 * 8 + 1) * ((self.H + 63) // 64 * 8 + 1)
+        self.region_stride = (self.W + 63) // 64 * 8 + 1
+        n, cells = self.region_stride * ((self.H + 63) // 64 * 8 + 1), (self.H // 4) * (self.W // 4) * self.hmod.CELL_DT.itemsize
         with torch.cuda.stream(hv.tstream):
             self.d_data = torch.zeros(n, dtype=torch.int8, device=hv.device)
             self.d_bs = torch.zeros(n, dtype=torch.uint8, device=hv.device)
-            self.d_cells = torch.zeros((self.H // 4) * (self.W // 4) * 16, dtype=torch.uint8, device=hv.device)
+            self.d_cells = torch.zeros(cells, dtype=torch.uint8, device=hv.device)
         self.d_chroma = hv.up(np.full(2 * (self.H // 2) * (self.W // 2), 128 << (self.bd - 8), self.dt))
+        if self.finish:
+            self.cqt_block, self.cqt_data, self.cqt_bs = hv.zeros(cells, np.uint8), hv.zeros(n, np.uint8), hv.zeros(n, np.uint8)     # (data: int8 values)
 
     def tree_and_filter_on_device(self):
         """the transform-tree decisions of every inter unit (both depths through residual + DCT -> RDOQ -> IQ + IDCT + add -> SSD, the decision by k_rqt_decide, every
@@ -1455,9 +1448,8 @@ class DecisionPicture:
                           self.sao_work, self.d_sao_params)
         hv.sao_decide_d(bd, q16, 7, self.d_pic, self.d_cpic, *sl, self.deblocked, self.cdeblocked, *sl, self.sao_dst, self.csao_dst, *sl, self.d_sao_ctus,
                         self.cx, self.d_sao_params, self.sao_ctx[0], self.sao_ctx[1], self.sao_decide_work, self.d_sao_decisions)
-        n64 = (W + 63) // 64 * 8 + 1
         hv.sao_apply_d(bd, 3, W, H, 6, self.deblocked, o, self.cdeblocked, co, self.cpe + co, self.stride, cs, self.recon, o, self.crecon, co, self.cpe + co,
-                       self.stride, cs, self.d_sao_decisions, None, self.d_data, n64)
+                       self.stride, cs, self.d_sao_decisions, None, self.d_data, self.region_stride)
         hv.pad_block_d(self.recon, o, W, H, self.stride, self.PAD)
         hv.pad_block_d(self.crecon, co, W // 2, H // 2, cs, c2)
         hv.pad_block_d(self.crecon, self.cpe + co, W // 2, H // 2, cs, c2)
@@ -1465,62 +1457,38 @@ class DecisionPicture:
     @property
     def sao_decisions(self):
         """the SAO decisions of the last sao=True step (SAO_DECISION_DT per 64x64 CTU in raster order): downloaded when asked for"""
-        if getattr(self, "_sao_decisions", None) is None:
-            self._sao_decisions = self.hv.down(self.d_sao_decisions, np.uint8).view(self.hmod.SAO_DECISION_DT).copy()
-        return self._sao_decisions
+        if "sao" not in self._cache:
+            self._cache["sao"] = self.hv.down(self.d_sao_decisions, np.uint8).view(self.hmod.SAO_DECISION_DT).copy()
+        return self._cache["sao"]
 
     def tree_decisions(self):
-        """the transform-tree part of tree_and_filter_on_device for self.units; returns the plan (its d_units / d_out are what the block structure is made from)"""
-        hv, bd = self.hv, self.bd
+        """the transform-tree part of tree_and_filter_on_device for self.units: the luma candidates of both depths through the chain into pieces, each size followed by
+        its level statistics (residual_rates=True: its CABAC rates), and the decision; tree_rates=True: chroma prediction, the luma and then the chroma candidates
+        (cIdx 1 / 2), the whole-tree rate and cbf mask per (unit size, depth), and the decision over three planes.  Then every candidate reconstructed again -- the
+        chosen trees' luma into recon and, with tree_rates, their chroma into crecon.  Returns the plan (its d_units / d_out are what the block structure is made from)"""
+        hv = self.hv
         if not hasattr(self, "rqt_plan"):
             self.rqt_plan = self._rqt_plan()
         P = self.rqt_plan
-        src = self.d_pic
+        luma, chroma = (self.d_pic, self.stride, self.pred, self.W), (self.d_cpic, self.cstride, self.cpred, self.W // 2)
+        units = (P["d_units"].view(-1, 4), P["d_zero_at"], P["d_one_at"], P["table"])
         if self.tree_rates:
-            return self._tree_decisions_three_planes(P)
-        for g in P["sizes"].values():
-            hv.tu_forward_d(bd, 0, g["log2"], g["coef"], src, self.stride, self.pred, self.W, g["d_jobs"].view(-1, 4))
-            hv.rdoq_d(bd, g["log2"], g["level"], g["coef"], self.d_states, g["d_rj"], g["cbf"], g["work"])
-            hv.tu_reconstruct_d(bd, 0, g["log2"], g["inv"], g["dshift"], g["piece"], g["nn"], self.pred, self.W, src, self.stride, g["level"], g["d_jobs"].view(-1, 4), g["ssd"])
-            if self.residual_rates:
-                hv.residual_rate_d(g["log2"], g["level"], self.d_states, g["d_qj"], g["rates"])
-            else:
-                hv.level_stats_d(g["level"], g["d_sj"], g["m"], g["stats"])
-        if self.residual_rates:
-            self._rqt_rates = None
-            hv.rqt_decide_rated_d(P["d_units"].view(-1, 4), P["d_zero_at"], P["d_one_at"], P["table"], P["rates"], self.origin, self.stride, P["dump"], P["rl_q16"], P["d_out"])
+            self.chroma_predict()
+            self._chain(P["sizes"].values(), *luma)
+            self._chain(P["csizes"].values(), *chroma)
+            self._tree_rates(P)
+            hv.rqt_decide_tree_d(*units, P["ctable"], P["d_chroma_at"], P["tree_rate"], P["tree_cbf"], self.origin, self.stride, P["dump"], self.corigin,
+                                 self.cpe + self.corigin, self.cstride, P["cdump"], P["rl_q16"], P["d_out"], P["d_tree_out"])
+            self._chain_final(P["sizes"].values(), *luma, self.recon, self.stride)
+            self._chain_final(P["csizes"].values(), *chroma, self.crecon, self.cstride)
+        elif self.residual_rates:
+            self._chain(P["sizes"].values(), *luma, then=lambda g: hv.residual_rate_d(g["log2"], g["level"], self.d_states, g["d_qj"], g["rates"]))
+            hv.rqt_decide_rated_d(*units, P["rates"], self.origin, self.stride, P["dump"], P["rl_q16"], P["d_out"])
+            self._chain_final(P["sizes"].values(), *luma, self.recon, self.stride)
         else:
-            hv.rqt_decide_d(P["d_units"].view(-1, 4), P["d_zero_at"], P["d_one_at"], P["table"], self.origin, self.stride, P["dump"], P["rl_q16"], P["d_out"])
-        for g in P["sizes"].values():
-            hv.tu_reconstruct_d(bd, 0, g["log2"], g["inv"], g["dshift"], self.recon, self.stride, self.pred, self.W, src, self.stride, g["level"], g["d_fin"].view(-1, 4), g["ssd2"])
-        return P
-
-    def _tree_decisions_three_planes(self, P):
-        """tree_rates=True: chroma prediction; the luma candidates as on the default route; the chroma candidates of both depths per chroma size (residual + DCT ->
-        RDOQ with cIdx 1 / 2 from the unit's snapshot -> IQ + IDCT + add -> SSD, into pieces); the whole-tree rate and cbf mask per (unit size, depth); the decision
-        over three planes; every candidate reconstructed again -- the chosen trees' luma into recon AND chroma into crecon"""
-        hv, bd, src, hw = self.hv, self.bd, self.d_pic, self.W // 2
-        self.chroma_predict()
-        for g in P["sizes"].values():
-            hv.tu_forward_d(bd, 0, g["log2"], g["coef"], src, self.stride, self.pred, self.W, g["d_jobs"].view(-1, 4))
-            hv.rdoq_d(bd, g["log2"], g["level"], g["coef"], self.d_states, g["d_rj"], g["cbf"], g["work"])
-            hv.tu_reconstruct_d(bd, 0, g["log2"], g["inv"], g["dshift"], g["piece"], g["nn"], self.pred, self.W, src, self.stride, g["level"], g["d_jobs"].view(-1, 4), g["ssd"])
-        for g in P["csizes"].values():
-            hv.tu_forward_d(bd, 0, g["log2"], g["coef"], self.d_cpic, self.cstride, self.cpred, hw, g["d_jobs"].view(-1, 4))
-            hv.rdoq_d(bd, g["log2"], g["level"], g["coef"], self.d_states, g["d_rj"], g["cbf"], g["work"])
-            hv.tu_reconstruct_d(bd, 0, g["log2"], g["inv"], g["dshift"], g["piece"], g["nn"], self.cpred, hw, self.d_cpic, self.cstride, g["level"], g["d_jobs"].view(-1, 4),
-                                g["ssd"])
-        for (L, depth), t in P["tree_jobs"].items():
-            hv.tree_rate_d(L, depth, P["sizes"][t["luma"]]["level"], P["csizes"][t["chroma"]]["level"], self.d_states, self.d_syntax_states, t["d_jobs"], P["tree_rate"],
-                           P["tree_cbf"])
-        self._rqt_rates = self._rqt_tree = None
-        hv.rqt_decide_tree_d(P["d_units"].view(-1, 4), P["d_zero_at"], P["d_one_at"], P["table"], P["ctable"], P["d_chroma_at"], P["tree_rate"], P["tree_cbf"], self.origin,
-                             self.stride, P["dump"], self.corigin, self.cpe + self.corigin, self.cstride, P["cdump"], P["rl_q16"], P["d_out"], P["d_tree_out"])
-        for g in P["sizes"].values():
-            hv.tu_reconstruct_d(bd, 0, g["log2"], g["inv"], g["dshift"], self.recon, self.stride, self.pred, self.W, src, self.stride, g["level"], g["d_fin"].view(-1, 4), g["ssd2"])
-        for g in P["csizes"].values():
-            hv.tu_reconstruct_d(bd, 0, g["log2"], g["inv"], g["dshift"], self.crecon, self.cstride, self.cpred, hw, self.d_cpic, self.cstride, g["level"], g["d_fin"].view(-1, 4),
-                                g["ssd2"])
+            self._chain(P["sizes"].values(), *luma, then=lambda g: hv.level_stats_d(g["level"], g["d_sj"], g["m"], g["stats"]))
+            hv.rqt_decide_d(*units, self.origin, self.stride, P["dump"], P["rl_q16"], P["d_out"])
+            self._chain_final(P["sizes"].values(), *luma, self.recon, self.stride)
         return P
 
     # ---- unit_trees=True: the transform tree of EVERY searched unit, made from the residual of its own winning prediction (what reconstructInter runs on after go2) ----
@@ -1530,16 +1498,13 @@ class DecisionPicture:
         cu_decisions and the node table.  Their predictions lie in UNIT PREDICTION PLANES: one luma allocation of four W x H planes and one chroma allocation of four
         (Cb, Cr) plane pairs, plane 6 - L for units of size 2^L, a unit's block at its picture position (stride W, W / 2 for chroma): a job of any launch names its
         block by a 32-bit offset, so one base pointer and stride serve a launch that mixes depth-0 blocks of size-L units with depth-1 blocks of size-(L + 1) units.
-        Per transform size the luma candidates (depth 0 of every unit of that size up to 32, then the four depth-1 blocks of every unit of the next larger size, 64
-        included); per chroma size the Cb / Cr candidates as _tree_plan lays them out; a 64x64 unit contributes its four 32x32 luma and four 16x16 Cb and Cr blocks
-        only.  tree_rate jobs per (L, depth): (6, 1) without the flag bit, 5..3 at both depths with it; out_index = 2 * unit + depth.  No final job records."""
+        The candidates are laid out as rqt_plan's are (_tree_tables); a 64x64 unit contributes its four 32x32 luma and four 16x16 Cb and Cr blocks only, and
+        its one tree-rate job, (6, 1), has no flag bit.  No final job records: nothing of these trees goes into a picture before the quadtree is committed."""
         if hasattr(self, "unit_plan"):
             return self.unit_plan
-        hv, hmod, torch, bd = self.hv, self.hmod, self.torch, self.bd
-        from . import workload
-        P = self._pu_plan()
+        hv, hmod, P = self.hv, self.hmod, self._pu_plan()
         pus, n = self.pus, len(self.pus)
-        W, hw, hh, c2 = self.W, self.W // 2, self.H // 2, self.PAD // 2
+        W, hw, hh = self.W, self.W // 2, self.H // 2
         if ((pus["x0"].astype(np.int64) + pus["w"] > W) | (pus["y0"].astype(np.int64) + pus["h"] > self.H)).any():
             raise ValueError("unit_trees=True needs every searched unit inside the picture")
         u = np.zeros(n, RQT_CU_DT)
@@ -1556,94 +1521,10 @@ class DecisionPicture:
             sel["cand_off"][g["sel"]] = np.stack([q["base"] + self.PU_CANDIDATES * i * q["size"] ** 2 for q in g["planes"]], 1)
         sel["dst_off"] = np.stack([uplane * ypl + uy * W + ux, 2 * uplane * cpl + (uy // 2) * hw + ux // 2, (2 * uplane + 1) * cpl + (uy // 2) * hw + ux // 2], 1)
         sel["log2_size"], sel["unit"] = uL, np.arange(n)
-        lists, clists = {s: [] for s in (2, 3, 4, 5)}, {s: [] for s in (2, 3, 4)}
-        zero_at, one_at, chroma_at = np.full(n, -1, np.int32), np.zeros(n, np.int32), np.zeros(n, hmod.RQT_CHROMA_AT_DT)
-        for i in range(n):
-            L, a = int(uL[i]), chroma_at[i]
-            if L < 6:
-                zero_at[i] = len(lists[L])
-                lists[L].append((i, 0, 0))
-                c0 = max(L - 1, 2)
-                a["cb_zero"], a["cr_zero"] = len(clists[c0]), len(clists[c0]) + 1
-                clists[c0] += [(i, 0, 1, 0), (i, 0, 2, 0)]
-            else:       # a 64x64 unit has no depth-0 candidate in any plane (its split is inferred)
-                a["cb_zero"], a["cr_zero"] = -1, -1
-            one_at[i] = len(lists[L - 1])
-            lists[L - 1] += [(i, 1, k) for k in range(4)]
-            if L > 3:
-                a["cb_one"], a["cr_one"] = len(clists[L - 2]), len(clists[L - 2]) + 4
-                clists[L - 2] += [(i, 1, comp, k) for comp in (1, 2) for k in range(4)]
-            else:
-                a["cb_one"], a["cr_one"] = a["cb_zero"], a["cr_zero"]
-        plan = dict(units=u, select_jobs=sel, zero_at=zero_at, one_at=one_at, chroma_at=chroma_at, sizes={}, csizes={}, tree_jobs={}, table=np.zeros((4, 5), np.uint64),
-                    ctable=np.zeros((4, 5), np.uint64), rl_q16=int((1.0 / self.lam) * 65536 + 0.5), launches=2,
-                    pred=hv.zeros(4 * ypl, self.dt), cpred=hv.zeros(8 * cpl, self.dt), d_units=hv.up(np.ascontiguousarray(u).view(np.int32)), d_zero_at=hv.up(zero_at),
-                    d_one_at=hv.up(one_at), d_chroma_at=hv.up(np.ascontiguousarray(chroma_at).view(np.int32)), d_out=hv.zeros(n * 26, np.int32),
-                    d_tree_out=hv.zeros(4 * n, np.int32), tree_cbf=hv.zeros(2 * n, np.int32), d_unit_cand=hv.zeros(n, np.int32))
-
-        def group(log2, jobs, ctx, c_idx):
-            m, area = len(jobs), 1 << 2 * log2
-            qs, qshift, _ = workload.quant_params(self.qp, log2, bd, False)
-            inv, dshift = workload.dequant_params(self.qp, log2, bd)
-            if c_idx is None:
-                qs, qshift, inv, dshift = (int(v) for v in self.quant[log2 - 2])
-            rj = np.zeros(m, hmod.RDOQ_JOB_DT)
-            rj["dst_off"] = rj["src_off"] = jobs[:, 0]
-            rj["quant_scale"], rj["quant_shift"], rj["inv_scale"] = qs, qshift, inv
-            rj["lambda_q16"], rj["sdh_factor"] = hmod.rdoq_lambda(self.lam, inv)
-            rj["sdh"], rj["ctx_index"] = 1, ctx
-            if c_idx is not None:
-                rj["c_idx"] = c_idx
-            with torch.cuda.stream(hv.tstream):
-                d_rj = torch.from_numpy(rj.view(np.uint8).reshape(-1)).to(hv.device)
-            return dict(log2=log2, nn=1 << log2, m=m, inv=inv, dshift=dshift, jobs=jobs, d_jobs=hv.up(jobs), d_rj=d_rj, coef=hv.zeros(m * area, np.int16),
-                        level=hv.zeros(m * area, np.int16), piece=hv.zeros(m * area, self.dt), work=hv.rdoq_workspace(m), cbf=hv.zeros(m, np.int32),
-                        ssd=hv.zeros(m, np.uint32))
-
-        for log2, cand in lists.items():
-            if not cand:
-                continue
-            nn, c = 1 << log2, np.array(cand, np.int64)
-            x = ux[c[:, 0]] + np.where(c[:, 1] == 1, (c[:, 2] & 1) * nn, 0)
-            y = uy[c[:, 0]] + np.where(c[:, 1] == 1, (c[:, 2] >> 1) * nn, 0)
-            at = np.arange(len(c)) << 2 * log2
-            jobs = np.stack([at, self.origin + y * self.stride + x, uplane[c[:, 0]] * ypl + y * W + x, at], 1).astype(np.int32)
-            g = plan["sizes"][log2] = group(log2, jobs, u["ctx_index"][c[:, 0]], None)
-            plan["table"][log2 - 2] = [g["cbf"].data_ptr(), g["ssd"].data_ptr(), 0, g["d_jobs"].data_ptr(), 0]
-            plan["launches"] += 3
-        for cl, cand in clists.items():
-            if not cand:
-                continue
-            cn, c = 1 << cl, np.array(cand, np.int64)
-            x = ux[c[:, 0]] // 2 + np.where(c[:, 1] == 1, (c[:, 3] & 1) * cn, 0)
-            y = uy[c[:, 0]] // 2 + np.where(c[:, 1] == 1, (c[:, 3] >> 1) * cn, 0)
-            comp, at = c[:, 2], np.arange(len(c)) << 2 * cl
-            jobs = np.stack([at, 3 * (comp - 1) * self.cpe + (y + c2) * self.cstride + x + c2, (2 * uplane[c[:, 0]] + comp - 1) * cpl + y * hw + x, at], 1).astype(np.int32)
-            g = plan["csizes"][cl] = group(cl, jobs, u["ctx_index"][c[:, 0]], comp)
-            g["cand"] = c
-            plan["ctable"][cl - 2] = [g["cbf"].data_ptr(), g["ssd"].data_ptr(), 0, g["d_jobs"].data_ptr(), 0]
-            plan["launches"] += 3
-        for L in (6, 5, 4, 3):
-            at = np.flatnonzero(uL == L)
-            if not len(at):
-                continue
-            c0, c1 = max(L - 1, 2), max(L - 2, 2)
-            for depth in ((1,) if L == 6 else (0, 1)):
-                tj = np.zeros(len(at), hmod.TREE_RATE_JOB_DT)
-                if depth == 0:
-                    tj["luma_off"], tj["cb_off"], tj["cr_off"] = zero_at[at] << 2 * L, chroma_at["cb_zero"][at] << 2 * c0, chroma_at["cr_zero"][at] << 2 * c0
-                else:
-                    tj["luma_off"], tj["cb_off"], tj["cr_off"] = one_at[at] << 2 * (L - 1), chroma_at["cb_one"][at] << 2 * c1, chroma_at["cr_one"][at] << 2 * c1
-                tj["ctx_index"], tj["out_index"], tj["sdh"] = u["ctx_index"][at], 2 * at + depth, 1
-                tj["flags"] = hmod.TREE_RATE_SPLIT_FLAG_CODED if L < 6 else 0      # above MaxTbLog2SizeY the split is inferred: no bin
-                with torch.cuda.stream(hv.tstream):
-                    d_tj = torch.from_numpy(tj.view(np.uint8).reshape(-1).copy()).to(hv.device)
-                plan["tree_jobs"][L, depth] = dict(jobs=tj, d_jobs=d_tj, luma=L - depth, chroma=c1 if depth else c0)
-                plan["launches"] += 1
-        with torch.cuda.stream(hv.tstream):
-            plan["tree_rate"] = torch.zeros(2 * n, dtype=torch.int64, device=hv.device)
-            plan["d_unit_rate"] = torch.zeros(n, dtype=torch.int64, device=hv.device)
-            plan["d_select_jobs"] = torch.from_numpy(sel.view(np.uint8).reshape(-1).copy()).to(hv.device)
+        plan = self._tree_tables(u, uplane, True)
+        plan.update(select_jobs=sel, d_select_jobs=self._up_records(sel), pred=hv.zeros(4 * ypl, self.dt), cpred=hv.zeros(8 * cpl, self.dt),
+                    d_unit_cand=hv.zeros(n, np.int32), d_unit_rate=self._zeros64(n),
+                    launches=2 + 3 * (len(plan["sizes"]) + len(plan["csizes"])) + len(plan["tree_jobs"]))      # (select and decide; a chain per size; a launch per tree job)
         self.unit_plan = plan
         return plan
 
@@ -1651,18 +1532,13 @@ class DecisionPicture:
         """behind pu_mode_launches: the winner's prediction of every searched unit into the unit prediction planes with its rate (one launch for every size), then per
         transform size the luma candidates and per chroma size the Cb / Cr candidates (residual + DCT -> RDOQ from the CTU's snapshot -> IQ + IDCT + add -> SSD, into
         pieces), the whole-tree rate and cbf mask per (unit size, depth), and the decision over three planes without final records.  Asynchronous"""
-        hv, bd, P, U = self.hv, self.bd, self._pu_plan(), self._unit_tree_plan()
+        hv, P, U = self.hv, self._pu_plan(), self._unit_tree_plan()
         hw = self.W // 2
-        hv.unit_pred_select_d(bd, P["d_cand_y"], P["d_cand_c"], U["pred"], self.W, U["cpred"], hw, P["d_first"], P["d_best"], P["d_rate"], U["d_select_jobs"],
+        hv.unit_pred_select_d(self.bd, P["d_cand_y"], P["d_cand_c"], U["pred"], self.W, U["cpred"], hw, P["d_first"], P["d_best"], P["d_rate"], U["d_select_jobs"],
                               U["d_unit_rate"], U["d_unit_cand"])
-        for groups, src, stride, pred, pstride in ((U["sizes"], self.d_pic, self.stride, U["pred"], self.W), (U["csizes"], self.d_cpic, self.cstride, U["cpred"], hw)):
-            for g in groups.values():
-                hv.tu_forward_d(bd, 0, g["log2"], g["coef"], src, stride, pred, pstride, g["d_jobs"].view(-1, 4))
-                hv.rdoq_d(bd, g["log2"], g["level"], g["coef"], self.d_states, g["d_rj"], g["cbf"], g["work"])
-                hv.tu_reconstruct_d(bd, 0, g["log2"], g["inv"], g["dshift"], g["piece"], g["nn"], pred, pstride, src, stride, g["level"], g["d_jobs"].view(-1, 4), g["ssd"])
-        for (L, depth), t in U["tree_jobs"].items():
-            hv.tree_rate_d(L, depth, U["sizes"][t["luma"]]["level"], U["csizes"][t["chroma"]]["level"], self.d_states, self.d_syntax_states, t["d_jobs"], U["tree_rate"],
-                           U["tree_cbf"])
+        self._chain(U["sizes"].values(), self.d_pic, self.stride, U["pred"], self.W)
+        self._chain(U["csizes"].values(), self.d_cpic, self.cstride, U["cpred"], hw)
+        self._tree_rates(U)
         hv.rqt_decide_units_d(U["d_units"].view(-1, 4), U["d_zero_at"], U["d_one_at"], U["table"], U["ctable"], U["d_chroma_at"], U["tree_rate"], U["tree_cbf"],
                               U["rl_q16"], U["d_out"], U["d_tree_out"])
 
@@ -1674,16 +1550,16 @@ class DecisionPicture:
         if not self.unit_trees:
             raise ValueError("unit_tree_decisions: the picture was made without unit_trees=True")
         hv, U, hmod = self.hv, self._unit_tree_plan(), self.hmod
-        if getattr(self, "_unit_tree_decisions", None) is None:
+        if "unit_trees" not in self._cache:
             with self.torch.cuda.stream(hv.tstream):
                 rate, unit_rate = U["tree_rate"].cpu().numpy().reshape(-1, 2), U["d_unit_rate"].cpu().numpy()
-            self._unit_tree_decisions = dict(units=U["units"], choice=hv.down(U["d_out"], np.int32).view(RQT_RESULT_DT).copy(),
+            self._cache["unit_trees"] = dict(units=U["units"], choice=hv.down(U["d_out"], np.int32).view(RQT_RESULT_DT).copy(),
                                              tree_choice=hv.down(U["d_tree_out"], np.int32).view(hmod.RQT_TREE_RESULT_DT).copy(), tree_rate=rate,
                                              tree_cbf=hv.down(U["tree_cbf"], np.int32).view(np.uint32).reshape(-1, 2), unit_rate=unit_rate,
                                              unit_cand=hv.down(U["d_unit_cand"], np.int32))
         if not planes:
-            return self._unit_tree_decisions
-        return dict(self._unit_tree_decisions, pred=hv.down(U["pred"], self.dt).reshape(4, self.H, self.W),
+            return self._cache["unit_trees"]
+        return dict(self._cache["unit_trees"], pred=hv.down(U["pred"], self.dt).reshape(4, self.H, self.W),
                     cpred=hv.down(U["cpred"], self.dt).reshape(4, 2, self.H // 2, self.W // 2))
 
     @property
@@ -1692,49 +1568,49 @@ class DecisionPicture:
         asked for"""
         if not self.tree_rates:
             raise ValueError("rqt_tree_results: the picture was made without tree_rates=True")
-        if getattr(self, "_rqt_tree", None) is None:
-            self._rqt_tree = self.hv.down(self.rqt_plan["d_tree_out"], np.int32).view(self.hmod.RQT_TREE_RESULT_DT).copy()
-        return self._rqt_tree
+        if "rqt_tree" not in self._cache:
+            self._cache["rqt_tree"] = self.hv.down(self.rqt_plan["d_tree_out"], np.int32).view(self.hmod.RQT_TREE_RESULT_DT).copy()
+        return self._cache["rqt_tree"]
 
     @property
     def rqt_results(self):
         """the transform-tree decisions of the last step (RQT_RESULT_DT per unit): downloaded when asked for"""
-        if getattr(self, "_rqt", None) is None:
-            self._rqt = self.hv.down(self.rqt_plan["d_out"], np.int32).view(RQT_RESULT_DT).copy()
-        return self._rqt
+        if "rqt" not in self._cache:
+            self._cache["rqt"] = self.hv.down(self.rqt_plan["d_out"], np.int32).view(RQT_RESULT_DT).copy()
+        return self._cache["rqt"]
 
     @rqt_results.setter
     def rqt_results(self, v):
-        self._rqt = v
+        self._cache["rqt"] = v
 
     @property
     def rqt_rates(self):
         """residual_rates=True: {log2: int64 Q16 rate of every candidate of that transform size} of the last step (the order of rqt_plan["sizes"][log2]'s jobs):
         downloaded when asked for"""
         if self.tree_rates:      # ... tree_rates=True: {(unit size, depth): the whole-tree rate of every unit of that size, in the order of rqt_plan["tree_jobs"]}
-            if getattr(self, "_rqt_rates", None) is None:
+            if "rqt_rates" not in self._cache:
                 with self.torch.cuda.stream(self.hv.tstream):
                     flat = self.rqt_plan["tree_rate"].cpu().numpy()
-                self._rqt_rates = {key: flat[t["jobs"]["out_index"]].copy() for key, t in self.rqt_plan["tree_jobs"].items()}
-            return self._rqt_rates
+                self._cache["rqt_rates"] = {key: flat[t["jobs"]["out_index"]].copy() for key, t in self.rqt_plan["tree_jobs"].items()}
+            return self._cache["rqt_rates"]
         if not self.residual_rates:
             raise ValueError("rqt_rates: the picture was made without residual_rates=True or tree_rates=True")
-        if getattr(self, "_rqt_rates", None) is None:
-            self._rqt_rates = {log2: self.hv.down(g["rates"], np.int64).copy() for log2, g in self.rqt_plan["sizes"].items()}
-        return self._rqt_rates
+        if "rqt_rates" not in self._cache:
+            self._cache["rqt_rates"] = {log2: self.hv.down(g["rates"], np.int64).copy() for log2, g in self.rqt_plan["sizes"].items()}
+        return self._cache["rqt_rates"]
 
     @property
     def cells(self):
         """the picture's block structure of the last step (CELL_DT [H / 4, W / 4]): on the device route k_block_cells leaves it in HBM and it is
         downloaded when asked for; the host route (search_on_device=False) made it on the host"""
-        if getattr(self, "_cells", None) is None:
+        if "cells" not in self._cache:
             from .havoc import CELL_DT
-            self._cells = self.hv.down(self.d_cells, np.uint8).view(CELL_DT).reshape(self.H // 4, self.W // 4).copy()
-        return self._cells
+            self._cache["cells"] = self.hv.down(self.d_cells, np.uint8).view(CELL_DT).reshape(self.H // 4, self.W // 4).copy()
+        return self._cache["cells"]
 
     @cells.setter
     def cells(self, v):
-        self._cells = v
+        self._cache["cells"] = v
 
     def block_cells(self, field, decisions):
         """the picture's block structure after the decisions, as the 4x4 cells havoc_mi355x_derive_bs reads: every unit one inter 2Nx2N
@@ -1753,13 +1629,6 @@ class DecisionPicture:
         """boundary strengths derived on the device from the block structure, in-loop deblocking of the reconstruction (luma; flat chroma planes
         stand in), padding: the reconstruction is then a reference picture.  Asynchronous."""
         hv, torch = self.hv, self.torch
-        n = ((self.W + 63) // 64 * 8 + 1) * ((self.H + 63) // 64 * 8 + 1)
-        if not hasattr(self, "d_bs"):
-            with torch.cuda.stream(hv.tstream):
-                self.d_data = torch.zeros(n, dtype=torch.int8, device=hv.device)
-                self.d_bs = torch.zeros(n, dtype=torch.uint8, device=hv.device)
-                self.d_cells = torch.zeros(cells.size * 16, dtype=torch.uint8, device=hv.device)
-            self.d_chroma = hv.up(np.full(2 * (self.H // 2) * (self.W // 2), 128 << (self.bd - 8), self.dt))
         with torch.cuda.stream(hv.tstream):
             self.d_cells.copy_(torch.from_numpy(cells.view(np.uint8).reshape(-1)), non_blocking=True)
         hv.derive_bs_d(self.d_cells, cells.shape[1], self.W, self.H, self.d_data, self.d_bs)
@@ -1781,9 +1650,7 @@ class DecisionPicture:
             with self.torch.cuda.stream(hv.tstream):
                 g["d_pj"].copy_(self.torch.from_numpy(pj.reshape(-1)), non_blocking=True)
             hv.pred_uni_d(8, bd, self.pred, self.W, ref0, self.stride, g["d_pj"].view(-1, 8), g["nn"], g["nn"])
-            hv.tu_forward_d(bd, 0, g["log2"], g["coef"], src, self.stride, self.pred, self.W, g["d_fj"])
-            hv.rdoq_d(bd, g["log2"], g["level"], g["coef"], self.d_states, g["d_rj"], g["cbf"], g["work"])
-            hv.tu_reconstruct_d(bd, 0, g["log2"], g["inv"], g["dshift"], self.recon, self.stride, self.pred, self.W, src, self.stride, g["level"], g["d_fj"], g["ssd"])
+            self._chain([g], src, self.stride, self.pred, self.W, self.recon, self.stride)
 
     def intra_decisions(self, on_device=True):
         """the intra side of the picture: per partition size the 35-mode SATD stage and its refinement order, then the RD refinement of every
@@ -1824,6 +1691,16 @@ class DecisionPicture:
                 state = self._graphs[key] = self.hv.graph_capture(fn)
             self.hv.graph_launch(state)
 
+    def _stages(self):
+        """the stages of STAGES this picture was made with, in step()'s order"""
+        return [s for s in STAGES if _on(s.option, getattr(self, s.option))]
+
+    def _forget(self):
+        """a step has run (or is about to be queued): nothing downloaded from the step before stands, of the picture or of its band views"""
+        self._cache.clear()
+        for v in getattr(self, "_views", ()):
+            v._cache.clear()
+
     def step(self):
         self.phase_planes()
         if self.temporal_mvp:
@@ -1840,33 +1717,20 @@ class DecisionPicture:
             # (running this on a second context / stream beside the searches -- it reads nothing they decide -- was measured: one picture alone 15.7 -> 15.5 ms, but
             # 294 -> 268 / 383 -> 237 pictures/s with 8 / 16 in flight: a second issuing thread per picture costs more than the overlap gives)
             self.intra_decisions()
-        self._merge = None
+        self._forget()
         if self.pu_modes:
             self.pu_candidates(res)
         if self.search_on_device:
             # everything after the searches is a FIXED sequence of launches over device-resident tables (the decided field never leaves the device, the decisions
             # between the launches are kernels): recorded once into a HIP graph, one launch per picture, one wait at the end
-            self._rqt = self._cells = self._sao_decisions = self._rqt_rates = self._rqt_tree = self._cu_decisions = self._cqt_decisions = None
-            self._unit_tree_decisions = self._cqt_commit = self._cqt_finish = self._cqt_motion = self._temporal = self._cqt_merge = None
-            pu = (self.pu_mode_launches,) if self.pu_modes else ()      # (the tables its launches read went up before the replay: pu_candidates)
-            pu += (self.unit_tree_launches,) if self.unit_trees else ()  # (behind pu_decide: it reads the winners in place; before cu_close, which reads its records)
-            pu += (self.cu_close_launches,) if self.cu_close else ()     # (after the tree decisions AND the prediction units' rates: it reads both in place)
-            pu += (self.cqt_launch,) if self.cqt else ()                 # (behind cu_close: it reads its records in place)
-            pu += (self.cqt_commit_launch,) if self.commit else ()       # (directly behind the quadtree: it acts on its records, into buffers of its own)
-            pu += (self.cqt_motion_launch,) if self.motion is not None else ()      # (directly behind the commit: it reads the cells that wrote, nothing else)
-            pu += (self.cqt_finish_launch,) if self.finish else ()       # (behind the commit: it filters and pads what that wrote, in place)
-            pu += (self.temporal_launch,) if self.col is not None and not self.temporal_mvp else ()      # (reads another picture's store and this picture's unit table
-                                                                                                         # only; with temporal_mvp it ran before the searches)
-            pu += (self.cqt_merge_launch,) if self.merge_lists is not None else ()      # (behind the commit, whose cells it reads, and the temporal candidates)
+            stages = [getattr(self, s.launch) for s in self._stages() if not (s.option == "col" and self.temporal_mvp)]      # (it ran before the searches)
             if self.sao:
-                self._replayed("after the searches", lambda: (self.merge_candidates(field), self.predict(field), self.sao_filter_inputs(field),
-                                                              self.sao_loop_filter(), [f() for f in pu]))
+                trees = lambda: (self.sao_filter_inputs(field), self.sao_loop_filter())
             elif self.tree_rates:      # (the chroma reconstruction is the tree decision's own: chroma_chain, which codes chroma at depth 0 always, does not run)
-                self._replayed("after the searches", lambda: (self.merge_candidates(field), self.predict(field), self.tree_and_filter_on_device(),
-                                                              [f() for f in pu]))
+                trees = self.tree_and_filter_on_device
             else:
-                self._replayed("after the searches", lambda: (self.merge_candidates(field), self.predict(field), self.tree_and_filter_on_device(),
-                                                              self.chroma_chain(field), [f() for f in pu]))
+                trees = lambda: (self.tree_and_filter_on_device(), self.chroma_chain(field))
+            self._replayed("after the searches", lambda: (self.merge_candidates(field), self.predict(field), trees(), [launch() for launch in stages]))
             self.rqt_stats = RqtStats()
             self.rqt_stats.launches, self.rqt_stats.candidates = self.rqt_plan["launches"], 5 * len(self.units)
         else:
@@ -1883,17 +1747,16 @@ class DecisionPicture:
     def _band_views(self, band_ctu_rows, side):
         """the picture's units cut into bands of whole CTU rows: per band a shallow copy of this object that owns the band's units, job tables and buffers and shares the
         picture's planes, field and block structure; its launches go to `side` (a Havoc context on a stream of another priority than the searches')"""
-        import copy
         key = (band_ctu_rows, id(side))
         if getattr(self, "_views_key", None) != key:
-            self._filter_buffers()
             rows = band_ctu_rows * 64
             views = []
             for y0 in range(0, self.H, rows):
-                v = copy.copy(self)
-                for name in ("mgroups", "pgroups", "cgroups", "rqt_plan", "d_merge_satd", "_merge", "_rqt", "_cells", "_views", "_views_key", "_graphs"):
-                    v.__dict__.pop(name, None)
-                v.hv, v._graphs, v.use_graphs = side, {}, True
+                # the picture as its constructor left it -- planes, field, snapshots, block structure: shared -- without anything built or downloaded since (plans,
+                # job tables, graphs, results: a view makes its own for its units)
+                v = object.__new__(type(self))
+                v.__dict__.update({name: self.__dict__[name] for name in self._constructed})
+                v.hv, v._graphs, v.use_graphs, v._cache = side, {}, True, {}
                 v.units = self.units[(self.units["y0"] >= y0) & (self.units["y0"] < y0 + rows)]
                 v.band_span = (y0, min(self.H, y0 + rows))
                 views.append(v)
@@ -1925,25 +1788,19 @@ class DecisionPicture:
             raise ValueError("step_banded does not price residuals with CABAC rates: use step() with residual_rates=True")
         if self.tree_rates:
             raise ValueError("step_banded does not price transform trees with CABAC rates: use step() with tree_rates=True")
-        if self.pu_modes:
-            raise ValueError("step_banded does not decide the prediction units' modes: use step() with pu_modes=True")
-        if self.cu_close:
-            raise ValueError("step_banded does not close coding units: use step() with cu_close=True")
-        if self.cqt:
-            raise ValueError("step_banded does not decide coding quadtrees: use step() with cqt=True")
-        if self.unit_trees:
-            raise ValueError("step_banded does not build the searched units' trees: use step() with unit_trees=True")
-        if self.col is not None:
-            raise ValueError("step_banded does not derive temporal candidates: use step() with col=")
+        for s in self._stages():
+            if s.banded is not None:
+                raise ValueError(s.banded)
         if self.sao:
             # SAO of band b reads the deblocked rows of band b + 1 (turing/TaskSao.cpp:46-56): not built
             raise ValueError("step_banded does not run SAO: use step() with sao=True")
         views = self._band_views(band_ctu_rows, side)
+        self._forget()
         if make_phase_planes:
             self.phase_planes()
         if not hasattr(self, "_dsearch"):
             n = len(self.pus)
-            self._dsearch = dict(pus=hv.up(np.ascontiguousarray(self.pus).view(np.uint8).reshape(-1)), first=hv.up(np.ascontiguousarray(self.ctu_first, np.int32)),
+            self._dsearch = dict(pus=self._pus_table(), first=hv.up(np.ascontiguousarray(self.ctu_first, np.int32)),
                                  out=hv.zeros(2 * n * RESULT_DT.itemsize, np.uint8), bi=hv.zeros(2 * n * RESULT_DT.itemsize, np.uint8),
                                  work=hv.zeros((self.hmod.search_workspace(W, H) + 3) // 4, np.int32), gave_up=hv.zeros(1, np.int32))
         D = self._dsearch
@@ -1960,7 +1817,7 @@ class DecisionPicture:
         side.tstream.wait_event(cleared)
         none = side.zeros(4, np.int32).view(-1, 4)[:0]
         side.block_cells_d(W, H, self.qp, 0, self.d_field, none, none, self.d_cells)      # blank cells, once; the bands add theirs
-        bstride = (W + 63) // 64 * 8 + 1
+        bstride = self.region_stride
         half = (H // 2) * (W // 2)
         for b, v in enumerate(views):
             y0, y1 = v.band_span
@@ -1999,7 +1856,6 @@ class DecisionPicture:
         hv.sync()
         side.sync()
         self.check_banded()
-        self._merge = self._rqt = self._cells = None
         res = hv.down(D["out"], np.uint8).view(RESULT_DT)
         self.bi_results = hv.down(D["bi"], np.uint8).view(RESULT_DT)
         field = hv.down(self.d_field, np.int16).reshape(2, (H + 3) // 4, (W + 3) // 4, 2)
@@ -2022,12 +1878,10 @@ class DecisionPicture:
         out = [dict(log2=g["log2"], coef=hv.down(g["coef"], np.int16), level=hv.down(g["level"], np.int16), cbf=hv.down(g["cbf"], np.int32),
                     ssd=hv.down(g["ssd"], np.uint32)) for g in self.groups]
         if self.pu_modes:
-            extra = dict(pu_modes=self.pu_decisions)
-            if self.cu_close:
-                extra["cu_close"] = self.cu_decisions
-            if self.cqt:
-                extra["cqt"] = self.cqt_decisions
-            if self.unit_trees:
-                extra["unit_trees"] = self.unit_tree_decisions()
+            extra = {}
+            for s in self._stages():
+                if s.extra is not None:
+                    value = getattr(self, s.extra)
+                    extra[s.option] = value() if callable(value) else value      # (unit_tree_decisions is a method: it takes planes=)
             return out, hv.down(self.recon, self.dt), extra
         return out, hv.down(self.recon, self.dt)
