@@ -33,6 +33,7 @@ __device__ __forceinline__ u32x4 ld16(const void *p)
 }
 __device__ __forceinline__ void st4(void *p, uint32_t v) { *reinterpret_cast<u32u *>(p) = v; }
 __device__ __forceinline__ void st8(void *p, u32x2 v) { *reinterpret_cast<u32x2u *>(p) = u32x2u{v.x, v.y}; }
+__device__ __forceinline__ void st16(void *p, u32x4 v) { *reinterpret_cast<u32x4u *>(p) = u32x4u{v.x, v.y, v.z, v.w}; }
 
 // ---- wave64 reductions.  DPP row operations + row broadcasts: no LDS traffic, result valid in lane 63,
 // then read back uniformly with readlane.
